@@ -9,7 +9,12 @@ One step = one pass of the hot path (patch-embed -> pre-LN -> 23 encoder layers 
 one batch of 256 synthetic images per GPU, inputs already resident in HBM.  Images are independent units, so the path
 shards over ranks with no data-path collective (weak scaling); value = images of ALL ranks / max-over-ranks time.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times exactly K steps and prints the headline line (ms_per_step = milliseconds per timed step).
+`--dump-outputs DIR` also writes what the last timed step returned (rank 0): DIR/features.npy, float32 [rows, 1024], the token
+rows of the [batch, 576, 1024] features - all of them up to DUMP_ROWS, else DUMP_ROWS rows drawn by a fixed seed in ascending order.
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+`--full` measures and adds the extra objects below to the line (--no-cpu-baseline, --cpu-images, --sweep*, --no-scores act only there):
   roofline      dominant kernel (the bf16 MFMA GEMM, fc1 shape): algorithmic FLOP per launch / its average launch
                 duration, timed with HIP events on the launch stream inside this run; peak = 2.5 PFLOP/s dense bf16.
   cpu_baseline  the CPU oracle (fp32 restatement of the reference's HF arithmetic, oracle/vit.py) on a bounded sample of
@@ -221,12 +226,30 @@ def aggregate_value(world, per_rank_units, steps, seconds):
     return world * per_rank_units * steps / seconds
 
 
+DUMP_ROWS = 8192                  # 8192 x 1024 float32 = 32 MiB
+
+
+def dump_outputs(dirname, feats):
+    """feats [B, T, d] (what one step returns) -> dirname/features.npy: float32 [min(B T, DUMP_ROWS), d], the token rows in (image, token)
+    order; above DUMP_ROWS rows a sample drawn without replacement by RandomState(0), the same for every run of the same batch."""
+    B, T, d = feats.shape
+    pick = np.arange(B * T)
+    if B * T > DUMP_ROWS:
+        pick = np.sort(np.random.RandomState(0).choice(B * T, DUMP_ROWS, replace=False))
+    pick = torch.from_numpy(pick).to(feats.device)
+    rows = feats[pick // T, pick % T].float().cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "features.npy"), rows)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=BATCH)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's features to DIR/features.npy (rank 0)")
+    ap.add_argument("--full", action="store_true", help="also measure the roofline, score kernels, fp32 tower, CPU baselines and sweep")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-images", type=int, default=8)                 # SURVEY §8(d): 8 of the same images
     ap.add_argument("--sweep", default="full", choices=["off", "reduced", "full"])
@@ -240,6 +263,8 @@ def main():
     ap.add_argument("--no-scores", action="store_true")
     ap.add_argument("--gemm-variant", type=int, default=int(os.environ.get("VISREP_GEMM_VARIANT", "5")), choices=[1, 2, 5, 6, 7])   # 6 / 7: the round-6 duo kernel (A/B only, profiles/round6_gemm.md)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     torch.set_num_threads(min(32, os.cpu_count() or 1))   # host-side weight packing: torch's default (128 here) thrashes, see cpu_baseline
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -273,6 +298,8 @@ def main():
 
     dt, feats = timed_steps(step, args.steps, args.warmup, dist, dev)
     assert torch.isfinite(feats.float()).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, feats)
 
     ms_per_step = dt / args.steps * 1e3
     value = aggregate_value(world, B, args.steps, dt)
@@ -280,7 +307,7 @@ def main():
 
     # ---- roofline of the dominant kernel, timed with HIP events on the launch stream
     roof, kern = None, {}
-    if rank == 0:
+    if args.full and rank == 0:
         M, d, m = B * spec.tokens, spec.d, spec.mlp
         # Operands = what the timed forward feeds these launches: the hidden state entering the middle encoder layer and that layer's weights
         # (LayerNorm gamma folded as the engine folds it), the MLP activations fc1 produces from them.  (Until round 4 these were N(0, 1)
@@ -509,7 +536,7 @@ def main():
         del x, hmlp, o1, o2, oqk, qk_act, vt
 
     scores = None
-    if rank == 0 and not args.no_scores:
+    if args.full and rank == 0 and not args.no_scores:
         try:
             scores = score_extras(dev)
             scores["fp32_tower"] = fp32_tower_extra(dev, spec, weights)
@@ -518,7 +545,7 @@ def main():
 
     # ---- CPU baseline: the oracle on a bounded sample, host cores of this box (rank 0, N=1 only)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_images > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_images > 0:
         from oracle import vit as OV
         n = args.cpu_images
         sample = px[:n].float().cpu()
@@ -553,7 +580,7 @@ def main():
     # depth (hidden_states[-2]: 23 layers), through the product's HOST twin (visrep_vit_forward_cpu: the explicit device="cpu" engine, plumbing -
     # neither the headline nor the cpu_baseline above, which is the oracle on this run's own images)
     cfg0 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             name0 = "openai/clip-vit-large-patch14"
             spec0 = VW.SPECS[name0]
@@ -588,15 +615,17 @@ def main():
                 "config": {"workload": "CLIP ViT-L/14-336 vision_tower feature-extract (hidden_states[-2], 23 layers run), "
                                        f"batch {B} per GPU, random-init weights, N(0,1) pixels resident in HBM",
                            "global_batch": world * B, "tokens": spec.tokens, "parallelism": f"dp{world} (image-sharded, no collective)", "gemm_variant": args.gemm_variant},
-                "roofline": roof, "cpu_baseline": cpu, "configs0_cpu": cfg0, "scores": scores, "sweep": sweep,
+                "full": args.full,
             }
+            if args.full:
+                line.update(roofline=roof, cpu_baseline=cpu, configs0_cpu=cfg0, scores=scores, sweep=sweep)
             print(json.dumps(line), flush=True)
 
     # ---- the 13-setting A + C sweep (all ranks take part; images sharded rank::world).  It is an extra on the headline line and has the
     # path's only collectives: a rank that fails alone would leave the others waiting in an all-gather, so a watchdog bounds it - on
     # expiry rank 0 prints the line it already has (sweep = the timeout) and every rank leaves without the final barrier.
     sweep = None
-    if args.sweep != "off":
+    if args.full and args.sweep != "off":
         import threading
         # The headline line is printed AFTER the sweep (one JSON line per run), so a sweep that hangs must not take it down with it: the watchdog
         # bounds it.  One GPU: the full sweep takes ~80 s with its setup (900 s allowed).  world > 1 has never run on hardware (RCCL all_to_all under

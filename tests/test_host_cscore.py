@@ -63,6 +63,7 @@ def cpu_mutual_nn(bank, img1, img2, P, chunk=2048, eps=1e-10):
 
 @pytest.fixture
 def cpu_ops(monkeypatch):
+    monkeypatch.setattr(PT, "device", "cpu")              # pck_train picks cuda when a GPU is visible: the stand-ins take host tensors
     monkeypatch.setattr(cscore_ops, "transfer", cpu_transfer)
     monkeypatch.setattr(cscore_ops, "pck_counts", cpu_pck_counts)
     monkeypatch.setattr(cscore_ops, "mutual_nn_distance", cpu_mutual_nn)
@@ -156,6 +157,7 @@ def _worker(rank, world, tmp, port, q):
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     cscore_ops.transfer, cscore_ops.pck_counts = cpu_transfer, cpu_pck_counts
+    PT.device = "cpu"
     root = os.path.join(tmp, "data", "SPair-71k")
     a = eval_args(root, 16)
     a.COMPUTE_GEOAWARE_METRICS = True                       # the geo-aware counters ride in the same all-reduce

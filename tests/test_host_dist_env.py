@@ -23,8 +23,15 @@ def test_no_launcher_means_no_process_group(monkeypatch):
     assert dist_env.init_from_env() is False and not torch.distributed.is_initialized()
 
 
-def _ascore_worker(rank, world, tmp, port, q):
+def _host_launch(rank, world, port):
+    """The launcher's environment on a host without a GPU (dist_env then brings up gloo), also where GPUs are visible: two ranks of nccl
+    would need two devices, and the stand-ins compute on host tensors."""
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    torch.cuda.is_available = lambda: False
+
+
+def _ascore_worker(rank, world, tmp, port, q):
+    _host_launch(rank, world, port)
     from law_of_vision_representation_in_mllms_amd.A_score import compute as AC
     AC._score_batch, AC._row_scales = _oracle_batch, _no_scales
     res = AC.main(["--base-folder", tmp, "--subfolders", "encA", "encB", "--n-images", "6", "--device", "cpu"])   # stand-in score hooks: device-agnostic
@@ -32,11 +39,12 @@ def _ascore_worker(rank, world, tmp, port, q):
 
 
 def _cscore_worker(rank, world, tmp, port, q):
-    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    _host_launch(rank, world, port)
     os.chdir(tmp)
     from law_of_vision_representation_in_mllms_amd import cscore_ops
     from law_of_vision_representation_in_mllms_amd.C_score import pck_train as PT
     cscore_ops.transfer, cscore_ops.pck_counts = cpu_transfer, cpu_pck_counts
+    PT.device = "cpu"
     cfg = os.path.join(os.path.dirname(PT.__file__), "configs", "eval_zero_shot_spair.yaml")
     args = PT.parse_args(["--config", cfg, "--DATA_DIR", os.path.join(tmp, "data", "SPair-71k"), "--NOTE", "dist"])
     args.DATA_DIR, args.NOTE = os.path.join(tmp, "data", "SPair-71k"), "dist"          # the yaml's keys override the command line

@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-r5p}; mkdir -p $O
 for r in 1 2; do for h in 0 1; do
-  VISREP_XCD_BALANCE=$h timeout 300 python bench.py --sweep off --no-cpu-baseline --no-scores --steps 10 --warmup 3 > $O/ab_xcd.$h.$r.json 2> $O/ab_xcd.$h.$r.err
+  VISREP_XCD_BALANCE=$h timeout 300 python bench.py --full --sweep off --no-cpu-baseline --no-scores --steps 10 --warmup 3 > $O/ab_xcd.$h.$r.json 2> $O/ab_xcd.$h.$r.err
   python - $O/ab_xcd.$h.$r.json $h $r <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r = d["roofline"]

@@ -4,8 +4,8 @@
 #   tests[:<pytest -k expression>]      python -m pytest tests -m gpu -x (whole suite, or the selection)
 #   testsall:<pytest -k expression>     the selection without -x and with -s (printed diagnostics kept)
 #   smoke                               __graft_entry__.smoke()
-#   bench[:<bench.py flags>]            bench.py (default: --sweep off --no-cpu-baseline --steps 10 --warmup 3); prints value / fractions
-#   benchfull                           the driver's line: python bench.py (full sweep, scores, CPU baseline)
+#   bench[:<bench.py flags>]            bench.py (default: --full --sweep off --no-cpu-baseline --steps 10 --warmup 3); prints value / fractions
+#   benchfull                           python bench.py --full (full sweep, scores, CPU baseline)
 #   ab:<lib-a>,<lib-b>[,...]            bench (sweep off) alternating over VISREP_LIB variant libraries (`default` = the product library), 2 rounds
 #   trace:<python file + args>          rocprofv3 --kernel-trace --stats of the command, summary via tools/summarize_pmc.py
 #   pmc:<counters,comma>:<python file>  one rocprofv3 --pmc pass (counters in their own run: never combined with a trace domain)
@@ -38,11 +38,11 @@ for step in "$@"; do
     testsall) timeout 1800 python -m pytest tests -m gpu -q --tb=line -s -k "$arg" > $O/$i.pytest.log 2>&1      # no -x, prints kept: a first look at a new test file
            echo "[$i testsall] rc=$?"; grep -E "^hostile|passed|failed" $O/$i.pytest.log | cut -c1-420 | tail -80 ;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/$i.smoke.log 2>&1; echo "[$i smoke] rc=$?"; tail -1 $O/$i.smoke.log ;;
-    bench) timeout 900 python bench.py ${arg:---sweep off --no-cpu-baseline --steps 10 --warmup 3} > $O/$i.bench.json 2> $O/$i.bench.err; echo "[$i bench] rc=$?"; short $O/$i.bench.json ;;
-    benchfull) timeout 2400 python bench.py > $O/$i.bench.json 2> $O/$i.bench.err; echo "[$i benchfull] rc=$?"; short $O/$i.bench.json ;;
+    bench) timeout 900 python bench.py ${arg:---full --sweep off --no-cpu-baseline --steps 10 --warmup 3} > $O/$i.bench.json 2> $O/$i.bench.err; echo "[$i bench] rc=$?"; short $O/$i.bench.json ;;
+    benchfull) timeout 2400 python bench.py --full > $O/$i.bench.json 2> $O/$i.bench.err; echo "[$i benchfull] rc=$?"; short $O/$i.bench.json ;;
     ab) for r in 1 2; do for v in ${arg//,/ }; do
           if [ $v = default ]; then unset VISREP_LIB; else export VISREP_LIB=$PWD/$P/libvisrep_hip_$v.so; fi
-          timeout 300 python bench.py --sweep off --no-cpu-baseline --no-scores --steps 10 --warmup 3 > $O/$i.ab.$v.$r.json 2> $O/$i.ab.$v.$r.err; echo "[$i ab $v $r] rc=$?"; short $O/$i.ab.$v.$r.json
+          timeout 300 python bench.py --full --sweep off --no-cpu-baseline --no-scores --steps 10 --warmup 3 > $O/$i.ab.$v.$r.json 2> $O/$i.ab.$v.$r.err; echo "[$i ab $v $r] rc=$?"; short $O/$i.ab.$v.$r.json
         done; done; unset VISREP_LIB ;;
     trace) rm -rf $O/$i.trace; timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$i.trace -- python $arg > $O/$i.trace.log 2>&1; echo "[$i trace] rc=$?"
            python tools/summarize_pmc.py $O/$i.trace > $O/$i.trace.md 2>/dev/null; head -30 $O/$i.trace.md ;;
