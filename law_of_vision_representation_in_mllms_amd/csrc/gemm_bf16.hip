@@ -257,7 +257,9 @@ int visrep_device() {
 // CUs the persistent kernels leave free (round 6): with world > 1 the C leg's all_to_all runs on RCCL's own kernels WHILE the next tower launch's
 // persistent GEMMs would otherwise own every CU (sweep.c_score_of); reserving k CUs (a multiple of 8: one or more per XCD) gives the collective
 // somewhere to run.  Process-wide, off by default (0): no multi-GPU box has been available to A/B it.  VISREP_RESERVE_CUS=k in the environment
-// or visrep_set_reserved_cus(k); grids captured into a HIP graph keep the size they were captured with.
+// or visrep_set_reserved_cus(k); grids captured into a HIP graph keep the size they were captured with: a graph captured at k = 0 and replayed
+// after the setter gives bitwise the same output, and results at any k are bitwise the k = 0 ones wherever the decomposition (whole launch / head +
+// tail rows, split-K slices, convolution kernel) is the same (tests/test_gpu_cu_counts.py) - so the setter does not warn.
 static std::atomic<int> g_reserved_cus{-1};
 static int reserved_cus() {
     int v = g_reserved_cus.load(std::memory_order_relaxed);
