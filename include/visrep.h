@@ -205,7 +205,17 @@ int visrep_mhsa_cls_fwd(const void* qk, int ldqk, const void* vt, int ldvt, cons
  * the diffusion VAE's mid-block attention, AutoencoderKL: 9216 latent pixels at 768 px) runs a wide-head kernel that needs whole key tiles
  * (Tk % 64 == 0), causal = 0 and scale > 0.
  * causal = 1 masks keys after the query position (HF CLIPTextTransformer's causal mask: the prompt encoder behind
- * pipe.encode_prompt, dift_sd.py:258-263).  scale <= 0 (head_dim 64 only): pre-scaled Q, as for visrep_mhsa_fwd. */
+ * pipe.encode_prompt, dift_sd.py:258-263).  scale <= 0 (head_dim 64 only): pre-scaled Q, as for visrep_mhsa_fwd.
+ * Pointers (all three attention entry points): none may be null; q / qk, k and vt must be 16-byte aligned, out and vcls 8-byte aligned -
+ * anything else is refused with VISREP_ERR_ARG before any launch.  Output rows are written with 16-byte stores when ldo % 8 == 0 and out is
+ * 16-byte aligned, with 8-byte stores otherwise; the results are bitwise the same.  Nothing outside [row, h * head_dim .. + head_dim) of the
+ * B * Tq output rows is written; K rows past the last key row and q / k columns outside the heads are never read.
+ * Non-finite data (tests/test_gpu_attention_contract.py): a masked key is not skipped, it enters P.V with weight exactly 0.  Masked SCORES
+ * are overwritten, so a NaN / Inf in the Q or K of one image never reaches another image.  A NaN / Inf in image b's V does: where key tiles
+ * are the global 64-key blocks (visrep_attention_fwd / visrep_mhsa_fwd with Tk % 64 != 0, keys not shared) the images that share a key
+ * tile with the bad key - b - 1 and / or b + 1 - get 0 * NaN = NaN in that head's column, while softmax(QK^T)V keeps it inside image b.
+ * Every other image, and every image when all data are finite, is bitwise independent of its neighbours.  V^T columns that belong to no
+ * key must be finite for the same reason. */
 int visrep_attention_fwd(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* out, int ldo, int B, int Tq,
                          int Tk, int H, int head_dim, int kv_shared, int causal, float scale, void* stream);
 

@@ -690,6 +690,11 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_wide(const AttnArgs p) {
 
 }  // namespace
 
+// global_load_lds and the bf16x8 Q loads move 16 bytes per lane (q, k, vt); the narrow store path and the CLS value rows move 8 (out, vcls)
+static bool attn_misaligned(uintptr_t mask, const void* a, const void* b = nullptr, const void* c = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & mask) != 0;
+}
+
 thread_local int t_visrep_attn_variant = 1;   // 1 = attn_fwd<ND> for every head width (default); 2 = attn_fwd_ab (attention_ab.hip, VISREP_EXPERIMENTS builds) for head width 64
 
 extern "C" int visrep_set_attn_variant(int variant) {          // per-thread; returns the previous value
@@ -708,6 +713,9 @@ extern "C" int visrep_attention_fwd(const void* q, int ldq, const void* k, int l
                                     int B, int Tq, int Tk, int H, int head_dim, int kv_shared, int causal, float scale, void* stream) {
     if (head_dim != 64 && head_dim != 128 && head_dim != 192 && head_dim != 512)
         return visrep_set_error(VISREP_ERR_SHAPE, "attention: head_dim must be 64, 128, 192 or 512 (pad narrower heads with zero weights)");
+    if (!q || !k || !vt || !out) return visrep_set_error(VISREP_ERR_ARG, "attention: null pointer");
+    if (attn_misaligned(15, q, k, vt)) return visrep_set_error(VISREP_ERR_ARG, "attention: q, k and vt must be 16-byte aligned");
+    if (attn_misaligned(7, out)) return visrep_set_error(VISREP_ERR_ARG, "attention: out must be 8-byte aligned");
     if (B <= 0 || Tq <= 0 || Tk <= 0 || H <= 0) return visrep_set_error(VISREP_ERR_SHAPE, "attention: empty problem");
     if ((ldq % 8) || (ldk % 8) || (ldvt % 64) || (ldo % 4)) return visrep_set_error(VISREP_ERR_SHAPE, "attention: bad leading dimension");
     const long Mk = kv_shared ? Tk : (long)B * Tk;
@@ -768,6 +776,8 @@ extern "C" int visrep_mhsa_cls_fwd(const void* qk, int ldqk, const void* vt, int
                                    int head_dim, void* stream) {
     if (head_dim != 64) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_cls: only head_dim 64 is implemented");
     if (!qk || !vt || !vcls || !out) return visrep_set_error(VISREP_ERR_ARG, "mhsa_cls: null pointer");
+    if (attn_misaligned(15, qk, vt)) return visrep_set_error(VISREP_ERR_ARG, "mhsa_cls: qk and vt must be 16-byte aligned");
+    if (attn_misaligned(7, vcls, out)) return visrep_set_error(VISREP_ERR_ARG, "mhsa_cls: vcls and out must be 8-byte aligned");
     if (B <= 0 || H <= 0 || !visrep_mhsa_cls_supported(T)) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_cls: needs T = 1 + a multiple of 64 (CLS + full key tiles)");
     if ((ldqk % 8) || (ldvt % 64) || (ldo % 4) || (ldvc % 4)) return visrep_set_error(VISREP_ERR_SHAPE, "attention: bad leading dimension");
     if (ldvt < B * (T - 1)) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_cls: ldvt must cover B (T - 1) columns");
