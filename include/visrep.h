@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define VISREP_VERSION 610   /* 610: visrep_cscore_transfer_packed2 / visrep_cscore_transfer2_cpu, the key-point transfer on two per-encoder banks (new exports only).  600 = round 6: reserved CUs, GEMM tile-walk knob, gemm variants 6-8, visrep_masked_nn_min_f32, window < 0 in the C-score transfers (new exports / newly accepted argument values only).  500 = round 5: device CU count, routing counters, MFMA probe, A-score reference arithmetic, host twins (new exports only).  410 = round 4: split-route `products`, stream-keyed scratch, per-thread knobs (changed signatures); 410: q_prescaled = 2, row-mapped GEMM, image-aligned / wide-head attention, conv + GroupNorm partials */
+#define VISREP_VERSION 620   /* 620: head widths other than 64 in the bf16 tower - visrep_vit_config grows head_dim / head_pad (struct change), visrep_mhsa_fwd takes head_dim 64 | 96 | 128, visrep_attention_fwd head_dim 96, route id 12; visrep_im2col and visrep_vit_forward_cpu no longer refuse an image side that is not a multiple of the patch - they floor the division as Conv2d does (newly accepted argument values).  610: visrep_cscore_transfer_packed2 / visrep_cscore_transfer2_cpu, the key-point transfer on two per-encoder banks (new exports only).  600 = round 6: reserved CUs, GEMM tile-walk knob, gemm variants 6-8, visrep_masked_nn_min_f32, window < 0 in the C-score transfers (new exports / newly accepted argument values only).  500 = round 5: device CU count, routing counters, MFMA probe, A-score reference arithmetic, host twins (new exports only).  410 = round 4: split-route `products`, stream-keyed scratch, per-thread knobs (changed signatures); 410: q_prescaled = 2, row-mapped GEMM, image-aligned / wide-head attention, conv + GroupNorm partials */
 
 enum { VISREP_BF16 = 0, VISREP_F32 = 1 };
 enum { VISREP_OK = 0, VISREP_ERR_ARG = -1, VISREP_ERR_SHAPE = -2, VISREP_ERR_LAUNCH = -3 };
@@ -83,7 +83,8 @@ enum {
     VISREP_ROUTE_ATTN_CLS = 9,       /* attn_fwd_cls (image-aligned CLS towers) */
     VISREP_ROUTE_CONV_HALO = 10,     /* conv3x3_halo: halo-resident 3x3 convolution with the input's GroupNorm + SiLU fused */
     VISREP_ROUTE_CONV_C8 = 11,       /* conv3x3_c8: the VAE's first convolution straight from 8-channel pixel tokens (no im2col) */
-    VISREP_ROUTE_COUNT = 12
+    VISREP_ROUTE_ATTN_96 = 12,       /* attn_fwd96 (head width 96: true widths 65 .. 96 zero-padded) */
+    VISREP_ROUTE_COUNT = 13
 };
 int visrep_debug_routes(long* out, int reset);
 /* Matrix-pipe ceiling of THIS device under THIS process' conditions: `iters` bursts of 32 dependent-free v_mfma_f32_16x16x32_bf16 per wave,
@@ -178,10 +179,12 @@ int visrep_gemm_bf16_resid_stats(const void* A, int lda, const void* W, int ldw,
                                  const void* resid, const float* ls, void* rt, void* partial, float eps, void* stream);
 
 /* ---- multi-head self-attention forward (HF CLIPAttention / Dinov2SelfAttention / SiglipAttention: softmax(QK^T
- * scale) V, fp32 softmax).  qk: [B*T, 2*H*64] bf16 (Q | K, head-major columns); vt: V^T as written by
- * visrep_gemm_bf16(..., VISREP_EPI_VT): [H*64, ldvt] with ldvt >= round_up(B*T, 64), % 64 == 0, columns beyond B*T
- * finite; out: [B*T, H*64] bf16.  head_dim must be 64.  scale <= 0: Q already carries scale * log2(e) (folded into the Q projection by
- * the caller): the kernel computes p = 2^(q.k - reference) with the reference subtracted inside the matrix pipe (accumulator init). */
+ * scale) V, fp32 softmax).  qk: [B*T, 2*H*head_dim] bf16 (Q | K, head-major columns: K starts at column H*head_dim); vt: V^T as written by
+ * visrep_gemm_bf16(..., VISREP_EPI_VT): [H*head_dim, ldvt] with ldvt >= round_up(B*T, 64), % 64 == 0, columns beyond B*T
+ * finite; out: [B*T, H*head_dim] bf16.  head_dim must be 64, 96 or 128 (the PADDED width of the buffers: a tower whose heads are 72 or 80
+ * wide packs zero rows up to 96, one with 97 .. 128 up to 128; `scale` is the true width's).  scale <= 0 (head_dim 64 only): Q already
+ * carries scale * log2(e) (folded into the Q projection by the caller): the kernel computes p = 2^(q.k - reference) with the reference
+ * subtracted inside the matrix pipe (accumulator init). */
 int visrep_mhsa_fwd(const void* qk, int ldqk, const void* vt, int ldvt, void* out, int ldo, int B, int T, int H, int head_dim,
                     float scale, void* stream);
 
@@ -200,8 +203,9 @@ int visrep_mhsa_cls_fwd(const void* qk, int ldqk, const void* vt, int ldvt, cons
  * self-attention (k/vt built from the same tokens, Tk = Tq) and cross-attention to the prompt (Tk = text length).
  * q: [B*Tq, ldq] bf16, head h in columns [h*head_dim, (h+1)*head_dim); k: [B*Tk, ldk] likewise ([Tk, ldk] when
  * kv_shared = 1: one key/value sequence - the prompt - serves every batch item); vt: [H*head_dim, ldvt] as written by
- * VISREP_EPI_VT over the key rows, ldvt >= round_up(key rows, 64); out: [B*Tq, ldo].  head_dim in {64, 128, 192}: the
- * weight packer zero-pads narrower heads (SD1.5: 40 / 80 / 160), which changes nothing in softmax(QK^T)V.  head_dim 512 (the single head of
+ * VISREP_EPI_VT over the key rows, ldvt >= round_up(key rows, 64); out: [B*Tq, ldo].  head_dim in {64, 96, 128, 192}: the
+ * weight packer zero-pads narrower heads (SD1.5: 40 / 80 / 160; SigLIP-so400m 72 and ViT-H/14 80 to 96), which changes nothing in
+ * softmax(QK^T)V.  head_dim 96 (attn_fwd96) runs 18 MFMAs per 64-key tile where 128 runs 24 and needs scale > 0.  head_dim 512 (the single head of
  * the diffusion VAE's mid-block attention, AutoencoderKL: 9216 latent pixels at 768 px) runs a wide-head kernel that needs whole key tiles
  * (Tk % 64 == 0), causal = 0 and scale > 0.
  * causal = 1 masks keys after the query position (HF CLIPTextTransformer's causal mask: the prompt encoder behind
@@ -220,6 +224,9 @@ int visrep_attention_fwd(const void* q, int ldq, const void* k, int ldk, const v
                          int Tk, int H, int head_dim, int kv_shared, int causal, float scale, void* stream);
 
 /* ---- patch embedding pieces (HF CLIPVisionEmbeddings / Dinov2Embeddings / SiglipVisionEmbeddings) */
+/* visrep_im2col: cols [B * (Himg / patch) * (Wimg / patch), Kpad] bf16, k = c p p + i p + j.  The grid is floor(side / patch), as
+ * Conv2d(kernel = stride = patch) gives it: the trailing Himg % patch rows and Wimg % patch columns are never read (384 / 14 = 27 patches,
+ * 6 pixels unused).  Since 620; before, a side that was not a multiple of the patch was refused. */
 int visrep_im2col(const void* pixels, int pixel_dtype, void* cols, int B, int Himg, int Wimg, int patch, int Kpad, void* stream);
 int visrep_cls_rows(void* x, int ldx, const float* cls, const float* pos, int B, int T, int d, void* stream);
 int visrep_cast_f32_bf16(const float* src, void* dst, long n, void* stream);
@@ -235,6 +242,12 @@ typedef struct {
      * projected by two row-mapped GEMMs, patch rows -> V^T, CLS rows -> [B, d]); other shapes behave as 1.  bf16 tower only; the fp32
      * towers ignore it. */
     int q_prescaled;
+    /* bf16 tower only (the fp32 and host towers use d / heads).  head_dim: the true head width d / heads (0 = d / heads), what the softmax
+     * scale head_dim^-0.5 is taken from.  head_pad: the width every head occupies in wqkv's q / k / v rows and in wo's columns, zero-padded
+     * by the packer (0 = head_dim): 64, 96 or 128, >= head_dim.  wqkv is then [3 * heads * head_pad, d] (Q | K | V blocks of heads * head_pad
+     * rows), bqkv / sqkv [3 * heads * head_pad], wo [d, heads * head_pad].  head_pad != 64 needs q_prescaled = 0.  `mlp` is the PADDED MLP
+     * width the w1 / b1 / s1 / w2 arrays have (zero rows / columns past the true width), a multiple of 128. */
+    int head_dim, head_pad;
 } visrep_vit_config;
 typedef struct {           /* device pointers; matrices bf16 [out,in], vectors fp32; ls1/ls2 NULL when no LayerScale */
     const float *ln1_g, *ln1_b; const void* wqkv; const float* bqkv; const void* wo; const float* bo; const float* ls1;

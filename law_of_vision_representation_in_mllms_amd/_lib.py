@@ -11,7 +11,7 @@ import threading
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VISREP_LIB") or os.path.join(_PKG, "libvisrep_hip.so")   # VISREP_LIB: diagnostic builds only
 
-ABI_VERSION = 610                 # include/visrep.h VISREP_VERSION this binding was written against (checked at load)
+ABI_VERSION = 620                 # include/visrep.h VISREP_VERSION this binding was written against (checked at load)
 BF16, F32 = 0, 1
 EPI_BIAS, EPI_ACT, EPI_RESID, EPI_VT, EPI_PATCH, EPI_F32 = range(6)
 ACT = {"none": 0, "quick_gelu": 1, "gelu": 2, "gelu_erf": 2, "gelu_tanh": 3, "gelu_pytorch_tanh": 3}
@@ -19,7 +19,8 @@ ACT = {"none": 0, "quick_gelu": 1, "gelu": 2, "gelu_erf": 2, "gelu_tanh": 3, "ge
 
 class VitConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("image_size", "patch", "d", "heads", "mlp", "layers", "tokens", "has_cls", "pre_ln",
-                                       "act", "kpad")] + [("eps", C.c_float), ("q_prescaled", C.c_int)]
+                                       "act", "kpad")] + [("eps", C.c_float), ("q_prescaled", C.c_int), ("head_dim", C.c_int),
+                                                                    ("head_pad", C.c_int)]
 
 
 class VitLayer(C.Structure):
@@ -173,7 +174,7 @@ def load(build_if_missing: bool = True):
         return lib
 
 
-ROUTES = ("gemm_256", "gemm_128", "gemm_tail", "splitk", "conv_256", "conv_128", "conv_128_gn", "attn", "attn_wide", "attn_cls", "conv_halo", "conv_c8")
+ROUTES = ("gemm_256", "gemm_128", "gemm_tail", "splitk", "conv_256", "conv_128", "conv_128_gn", "attn", "attn_wide", "attn_cls", "conv_halo", "conv_c8", "attn_96")
 
 
 def xcd_balance() -> dict:

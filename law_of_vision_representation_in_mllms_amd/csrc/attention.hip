@@ -1,4 +1,5 @@
-// Fused multi-head attention forward on gfx950 (no mask, full softmax): ViT self-attention (head width 64) and the
+// Fused multi-head attention forward on gfx950 (no mask, full softmax): ViT self-attention (head width 64; 96 for the towers whose heads
+// are 65 .. 96 wide, attn_fwd96 below) and the
 // UNet self- / cross-attention of the diffusion towers (head width D = 64*ND, narrower heads zero-padded by the weight
 // packer; key/value sequence of its own length Tk, optionally SHARED by all batch items - the prompt).
 //
@@ -462,6 +463,177 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_cls(const AttnClsArgs p) {
 }
 
 
+// ---- head width 96 (true widths 65 .. 96 zero-padded by the weight packer: SigLIP-so400m 72, ViT-H/14 80, ViT-g/14 88, DiT 72).  The flash
+// loop of attn_fwd (plain scale, deferred running maximum) with six 16-wide k-slices for Q.K^T and three 32-wide O tiles for P.V: 18 MFMAs
+// per 64-key tile where the 128-padded route runs 24 (a true-72 head: 25 % of the matrix work on padding instead of 44 %), 24 Q registers
+// and 48 accumulators, 24 KB of K / V^T per stage instead of 32.  The head stride is 96 elements = 192 bytes: every fragment stays 16-byte
+// aligned.  LDS images of a stage:
+//   K   : three THIRDS of [64 keys x 32 d]: rows of 64 B = four 16-B slots, row r at byte 64 r, logical slot s in physical slot
+//         s ^ ((r >> 2) & 3).  One LDS-DMA piece per wave fills 16 rows of a third (lane -> row tid >> 2, slot tid & 3).  A fragment read
+//         takes row 32 kt2 + lq, logical slot 2 (kk & 1) + hi of third kk >> 1.  Bank argument: a ds_read_b128 is served in four groups of
+//         16 lanes ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32) over a 256-B bank row = four 64-B key rows.  Inside a group
+//         hi and hence the logical slot are one value; the four lanes that share lq & 3 (the same 64-B quarter of the bank row) have
+//         (lq >> 2) & 3 = {0, 3, 1, 2} resp. {1, 2, 0, 3}: four different physical slots, so the 16 lanes cover 16 different 16-B slots.
+//   V^T : three blocks of [32 d x 64 keys]: 128-B rows with the (row >> 1) & 7 swizzle of attn_fwd (same reads, same argument, dt = 0..2).
+// Key tiles, masks, the XCD remap, the perm16 P operand and the store tail are attn_fwd's.  Pre-scaled Q is not built here.
+__global__ __launch_bounds__(256, 2) void attn_fwd96(const AttnArgs p) {
+    constexpr int D = 96, THIRD_B = 4096, KV_B = 3 * THIRD_B, STAGE_B = 2 * KV_B;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lq = lane & 31, hi = lane >> 5;
+    const int nqt = (p.Tq + 127) >> 7;
+    int id = xcd_remap(blockIdx.x, gridDim.x);
+    const int qt = id % nqt; id /= nqt;
+    const int h = id % p.H;
+    const int b = id / p.H;
+    const int tok0 = p.kv_shared ? 0 : b * p.Tk, tok1 = tok0 + p.Tk;   // this item's global key range
+
+    const int qloc = qt * 128 + wave * 32 + lq;
+    const size_t qrow = (size_t)b * p.Tq + (qloc < p.Tq ? qloc : p.Tq - 1);
+    bf16x8 qf[6];
+#pragma unroll
+    for (int kk = 0; kk < 6; ++kk) qf[kk] = *reinterpret_cast<const bf16x8*>(p.q + qrow * p.ldq + h * D + kk * 16 + hi * 8);
+
+    // ---- staging: K = 3 thirds x (64 rows x 4 slots), V^T = 3 blocks x (32 rows x 8 slots): one chunk per thread each
+    const int krow = tid >> 2, kslot = (tid & 3) ^ ((krow >> 2) & 3);
+    const int srow = tid >> 3, lslot = (tid & 7) ^ ((srow >> 1) & 7);
+    const int m_begin = tok0 & ~63;
+    const int ntile = (((tok1 + 63) & ~63) - m_begin) >> 6;
+    const bf16_t* kcur = p.k + h * D + kslot * 8 + (size_t)(m_begin + krow) * p.ldk;
+    const bf16_t* vcur = p.vt + (size_t)(h * D + srow) * p.ldvt + lslot * 8 + m_begin;
+    const size_t kstep = (size_t)KT * p.ldk, vblk = (size_t)32 * p.ldvt;
+    int mt_stage = m_begin;
+    auto stage = [&](int buf) {
+        char* sk = smem + buf * STAGE_B + wave * 1024;
+        char* sv = sk + KV_B;
+        const int mk = mt_stage + krow;                      // rows past the last key row are masked below: re-read the last row
+        const bf16_t* kr = mk < p.Mk ? kcur : kcur - (size_t)(mk - (p.Mk - 1)) * p.ldk;
+#pragma unroll
+        for (int t = 0; t < 3; ++t) glds16(kr + t * 32, sk + t * THIRD_B);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) glds16(vcur + t * vblk, sv + t * THIRD_B);
+        kcur += kstep; vcur += KT; mt_stage += KT;
+    };
+
+    const int ksw = (lq >> 2) & 3, kbase = lq * 64;          // K thirds: row 32 kt2 + lq, logical slot s -> physical s ^ ksw
+    const int rsw = (lq >> 1) & 7, rbase = lq * 128;         // V^T blocks: as attn_fwd
+
+    f32x16 o[3];
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt) o[dt] = f32x16{};
+    float m_run = -INFINITY, l_run = 0.f;
+
+    stage(0);
+    __syncthreads();
+    if (qt * 128 + wave * 32 >= p.Tq) {                      // an empty wave only stages its share and meets the barriers
+        for (int it = 0; it < ntile; ++it) {
+            if (it + 1 < ntile) stage((it & 1) ^ 1);
+            __syncthreads();
+        }
+        return;
+    }
+    for (int it = 0; it < ntile; ++it) {
+        const int cur = it & 1;
+        if (it + 1 < ntile) stage(cur ^ 1);
+        const char* sk = smem + cur * STAGE_B;
+        const char* sv = sk + KV_B;
+
+        f32x16 s[2];
+        s[0] = f32x16{}; s[1] = f32x16{};
+#pragma unroll
+        for (int kk = 0; kk < 6; ++kk)
+#pragma unroll
+            for (int kt2 = 0; kt2 < 2; ++kt2) {
+                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + (kk >> 1) * THIRD_B + kt2 * 2048 + kbase + (((2 * (kk & 1) + hi) ^ ksw) << 4));
+                s[kt2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], s[kt2], 0, 0, 0);
+            }
+        const int mt = m_begin + it * KT;
+        if ((mt < tok0) || (mt + KT > tok1) || p.causal) {   // wave-uniform
+#pragma unroll
+            for (int kt2 = 0; kt2 < 2; ++kt2)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = mt + kt2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    if (key < tok0 || key >= tok1 || (p.causal && key - tok0 > qloc)) s[kt2][r] = -INFINITY;
+                }
+        }
+        float mloc = fmaxf(fmaxf(s[0][0], s[0][1]), s[0][2]), mloc1 = fmaxf(fmaxf(s[1][0], s[1][1]), s[1][2]);
+#pragma unroll
+        for (int r = 3; r < 15; r += 2) {
+            mloc = fmaxf(fmaxf(mloc, s[0][r]), s[0][r + 1]);
+            mloc1 = fmaxf(fmaxf(mloc1, s[1][r]), s[1][r + 1]);
+        }
+        mloc = fmaxf(fmaxf(mloc, s[0][15]), fmaxf(mloc1, s[1][15]));
+        {
+            const unsigned u = __builtin_bit_cast(unsigned, mloc);
+            const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+            mloc = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
+        }
+#if VISREP_ATTN_V1_THR > 0                                  // deferred maximum, as attn_fwd
+        const float m_new = __any((mloc - m_run) * p.sc > (float)VISREP_ATTN_V1_THR) ? fmaxf(m_run, mloc) : m_run;
+#else
+        const float m_new = fmaxf(m_run, mloc);
+#endif
+        const float msc = m_new * p.sc;
+        float psum = 0.f;
+        uint32_t pb[2][8];
+#pragma unroll
+        for (int kt2 = 0; kt2 < 2; ++kt2)
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const float p0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt2][r], p.sc, -msc));
+                const float p1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt2][r + 1], p.sc, -msc));
+                psum += p0 + p1;
+                pb[kt2][r >> 1] = pack_bf16(p0, p1);
+            }
+        if (__any(m_new > m_run)) {                          // wave-uniform
+            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.sc);
+            l_run *= alpha;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int dt = 0; dt < 3; ++dt) o[dt][r] *= alpha;
+            m_run = m_new;
+        }
+        l_run += psum;
+
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const u32x4 w = {pb[c >> 1][4 * (c & 1) + 0], pb[c >> 1][4 * (c & 1) + 1], pb[c >> 1][4 * (c & 1) + 2], pb[c >> 1][4 * (c & 1) + 3]};
+            const bf16x8 pf = __builtin_bit_cast(bf16x8, w);
+#pragma unroll
+            for (int dt = 0; dt < 3; ++dt) {
+                const bf16x8 vf = *reinterpret_cast<const bf16x8*>(sv + dt * THIRD_B + rbase + (((2 * c + hi) ^ rsw) << 4));
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[dt], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+
+    l_run += __shfl_xor(l_run, 32);
+    const float inv = 1.f / l_run;
+    bf16_t* orow = p.out + ((size_t)b * p.Tq + (qloc < p.Tq ? qloc : p.Tq - 1)) * p.ldo + h * D;
+    const bool wide = (p.ldo & 7) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0;          // uniform
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+        for (int rg = 0; rg < 4; rg += 2) {
+            u32x2 a = {pack_bf16(o[dt][4 * rg + 0] * inv, o[dt][4 * rg + 1] * inv), pack_bf16(o[dt][4 * rg + 2] * inv, o[dt][4 * rg + 3] * inv)};
+            u32x2 c = {pack_bf16(o[dt][4 * rg + 4] * inv, o[dt][4 * rg + 5] * inv), pack_bf16(o[dt][4 * rg + 6] * inv, o[dt][4 * rg + 7] * inv)};
+            if (wide) {
+                const auto w0 = __builtin_amdgcn_permlane32_swap(a[0], c[0], false, false);
+                const auto w1 = __builtin_amdgcn_permlane32_swap(a[1], c[1], false, false);
+                if (qloc < p.Tq) {
+                    const u32x4 q4 = {(unsigned)w0[0], (unsigned)w1[0], (unsigned)w0[1], (unsigned)w1[1]};
+                    *reinterpret_cast<u32x4*>(orow + dt * 32 + (rg + hi) * 8) = q4;
+                }
+            } else if (qloc < p.Tq) {
+                *reinterpret_cast<u32x2*>(orow + dt * 32 + rg * 8 + hi * 4) = a;
+                *reinterpret_cast<u32x2*>(orow + dt * 32 + (rg + 1) * 8 + hi * 4) = c;
+            }
+        }
+}
+
 // ---- wide-head attention (head width D = 64 ND up to 512: the single 512-wide head of the diffusion VAE's mid-block attention over all 9216
 // latent pixels, AutoencoderKL encoder).  The flash loop of attn_fwd with the register file of ONE wave per SIMD: 32 Q fragments (128 VGPRs) and
 // the 32 x 512 output accumulators (256 registers) stay resident; a K tile and a V^T tile (64 keys x 512 = 64 KB each) are single-buffered
@@ -711,8 +883,8 @@ extern "C" int visrep_set_attn_variant(int variant) {          // per-thread; re
 
 extern "C" int visrep_attention_fwd(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* out, int ldo,
                                     int B, int Tq, int Tk, int H, int head_dim, int kv_shared, int causal, float scale, void* stream) {
-    if (head_dim != 64 && head_dim != 128 && head_dim != 192 && head_dim != 512)
-        return visrep_set_error(VISREP_ERR_SHAPE, "attention: head_dim must be 64, 128, 192 or 512 (pad narrower heads with zero weights)");
+    if (head_dim != 64 && head_dim != 96 && head_dim != 128 && head_dim != 192 && head_dim != 512)
+        return visrep_set_error(VISREP_ERR_SHAPE, "attention: head_dim must be 64, 96, 128, 192 or 512 (pad narrower heads with zero weights)");
     if (!q || !k || !vt || !out) return visrep_set_error(VISREP_ERR_ARG, "attention: null pointer");
     if (attn_misaligned(15, q, k, vt)) return visrep_set_error(VISREP_ERR_ARG, "attention: q, k and vt must be 16-byte aligned");
     if (attn_misaligned(7, out)) return visrep_set_error(VISREP_ERR_ARG, "attention: out must be 8-byte aligned");
@@ -744,6 +916,11 @@ extern "C" int visrep_attention_fwd(const void* q, int ldq, const void* k, int l
     if (ps && head_dim != 64) return visrep_set_error(VISREP_ERR_ARG, "attention: pre-scaled Q (scale <= 0) is built for head_dim 64");
     const int nqt = (Tq + 127) / 128, nd = head_dim / 64;
     const dim3 grid(nqt * H * B), block(256);
+    if (head_dim == 96) {                                   // attn_fwd96: 2 stages x (12 KB of K + 12 KB of V^T)
+        visrep_count_route(VISREP_ROUTE_ATTN_96);
+        hipLaunchKernelGGL(attn_fwd96, grid, block, (size_t)4 * 3 * 4096, (hipStream_t)stream, a);
+        return hipGetLastError() == hipSuccess ? 0 : visrep_set_error(VISREP_ERR_LAUNCH, "attention: launch failed");
+    }
     size_t lds = (size_t)nd * 4 * TILE_B;                   // double-buffered K + V^T tiles
 #ifdef VISREP_EXPERIMENTS
     {   // diagnostic (tools-only build): unused LDS to lower the number of resident workgroups per CU; the knob is read once
@@ -791,6 +968,6 @@ extern "C" int visrep_mhsa_cls_fwd(const void* qk, int ldqk, const void* vt, int
 
 extern "C" int visrep_mhsa_fwd(const void* qk, int ldqk, const void* vt, int ldvt, void* out, int ldo,
                                int B, int T, int H, int head_dim, float scale, void* stream) {
-    if (head_dim != 64) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa: only head_dim 64 is implemented");
-    return visrep_attention_fwd(qk, ldqk, (const bf16_t*)qk + (size_t)H * 64, ldqk, vt, ldvt, out, ldo, B, T, T, H, 64, 0, 0, scale, stream);
+    if (head_dim != 64 && head_dim != 96 && head_dim != 128) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa: head_dim must be 64, 96 or 128");
+    return visrep_attention_fwd(qk, ldqk, (const bf16_t*)qk + (size_t)H * head_dim, ldqk, vt, ldvt, out, ldo, B, T, T, H, head_dim, 0, 0, scale, stream);
 }

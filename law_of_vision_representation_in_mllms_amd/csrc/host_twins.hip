@@ -114,7 +114,8 @@ extern "C" int visrep_vit_forward_cpu(const visrep_vit_config* c, const visrep_v
     if (n_layers < 0 || n_layers > c->layers) return visrep_set_error(VISREP_ERR_ARG, "vit_forward_cpu: n_layers out of range");
     if (c->heads <= 0 || c->d % c->heads) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_cpu: d must be a multiple of heads");
     const int grid = c->image_size / c->patch, P = grid * grid, T = c->tokens, d = c->d, p = c->patch, S = c->image_size;
-    if (grid * c->patch != S || P + (c->has_cls ? 1 : 0) != T) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_cpu: tokens != grid^2 + cls");
+    // S / patch floors like Conv2d(k = s = patch): trailing pixels fill no patch (384 / 14 = 27)
+    if (grid <= 0 || P + (c->has_cls ? 1 : 0) != T) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_cpu: tokens != grid^2 + cls");
     const int kp = 3 * p * p, kpad = c->kpad > 0 ? c->kpad : kp;       // patch_w rows are kpad floats wide (zero padded past 3 p p)
     if (kpad < kp) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_cpu: kpad < 3 * patch^2");
     const long M = (long)B * T;

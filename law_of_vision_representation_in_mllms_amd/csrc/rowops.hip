@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void ln_stats_finalize_rows(const float2* __re
 
 // ------------------------------------------------------------------------------------------------ im2col
 // pixels [B, 3, H, W] (fp32 or bf16) -> cols [B*gh*gw, Kpad] bf16 with k = c*p*p + i*p + j (Conv2d weight order),
-// zero-filled for k >= 3*p*p.  One thread per 8 output elements (16-B store).
+// zero-filled for k >= 3*p*p; gh = H / p, gw = W / p floored (the last H % p rows and W % p columns are never read).  One thread per 8 output elements (16-B store).
 template <typename TIN>
 __global__ __launch_bounds__(256) void im2col_patches(const TIN* __restrict__ px, bf16_t* __restrict__ cols, int B, int Himg,
                                                       int Wimg, int patch, int Kpad) {
@@ -192,8 +192,9 @@ int visrep_ln_stats_finalize(const float2* partial, int slots, float2* rt, int r
 extern "C" int visrep_im2col(const void* pixels, int pixel_dtype, void* cols, int B, int Himg, int Wimg, int patch, int Kpad,
                              void* stream) {
     if (B <= 0) return 0;
-    if (Himg % patch || Wimg % patch || Kpad % 8 || Kpad < 3 * patch * patch)
-        return visrep_set_error(VISREP_ERR_SHAPE, "im2col: image must be a multiple of the patch, Kpad >= 3*p*p and % 8");
+    // Himg / patch floors like Conv2d(k = s = patch): trailing pixels that fill no patch are dropped (384 / 14 = 27 patches, 6 pixels unused)
+    if (patch <= 0 || Himg < patch || Wimg < patch || Kpad % 8 || Kpad < 3 * patch * patch)
+        return visrep_set_error(VISREP_ERR_SHAPE, "im2col: image must hold at least one patch, Kpad >= 3*p*p and % 8");
     const long total = (long)B * (Himg / patch) * (Wimg / patch) * (Kpad / 8);
     const int grid = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
     if (pixel_dtype == VISREP_F32)

@@ -271,16 +271,20 @@ struct Ws {
     size_t h, qk, vt, vcls, mlp, rt, part, total;
     int ldvt;
 };
+// true and padded head width of the bf16 tower (0 = derived: d / heads, no padding) and the attention side's width da = heads * padded
+inline int vit_head_dim(const visrep_vit_config* c) { return c->head_dim > 0 ? c->head_dim : (c->heads > 0 ? c->d / c->heads : 0); }
+inline int vit_head_pad(const visrep_vit_config* c) { return c->head_pad > 0 ? c->head_pad : vit_head_dim(c); }
 Ws layout(const visrep_vit_config* c, int B) {
     Ws w;
     const size_t M = (size_t)B * c->tokens;
     const size_t Mp = up(M, 128);
+    const size_t da = (size_t)c->heads * vit_head_pad(c), dh = da > (size_t)c->d ? da : (size_t)c->d;   // da == d for 64-wide heads
     w.ldvt = (int)(up(M, 64) + 64);
     size_t off = 0;
-    w.h = off;   off += up(Mp * c->d * 2, 256);
-    w.qk = off;  off += up(Mp * 2 * c->d * 2, 256);
-    w.vt = off;  off += up((size_t)c->d * w.ldvt * 2, 256);
-    w.vcls = off; off += up((size_t)B * c->d * 2, 256);              // V rows of the CLS tokens (image-aligned attention)
+    w.h = off;   off += up(Mp * dh * 2, 256);                       // LayerNorm output [M, d] / attention output [M, da]
+    w.qk = off;  off += up(Mp * 2 * da * 2, 256);
+    w.vt = off;  off += up(da * w.ldvt * 2, 256);
+    w.vcls = off; off += up((size_t)B * da * 2, 256);               // V rows of the CLS tokens (image-aligned attention)
     const size_t mlp_b = Mp * c->mlp * 2;
     const size_t cols_b = up((size_t)B * (c->tokens - c->has_cls), 128) * c->kpad * 2;
     w.mlp = off; off += up(mlp_b > cols_b ? mlp_b : cols_b, 256);   // im2col columns alias the MLP buffer
@@ -303,8 +307,14 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
     if (!c || !w || !pixels || !hidden || !workspace) return visrep_set_error(VISREP_ERR_ARG, "vit_forward: null pointer");
     if (B <= 0) return 0;
     if (n_layers < 0 || n_layers > c->layers) return visrep_set_error(VISREP_ERR_ARG, "vit_forward: n_layers out of range");
-    if (c->d != c->heads * 64) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: head_dim must be 64");
-    if (c->d % 128 || c->mlp % 128 || c->kpad % 64) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: d, mlp % 128 and kpad % 64 required");
+    const int hd = vit_head_dim(c), dp = vit_head_pad(c);
+    if (c->heads <= 0 || c->d != c->heads * hd) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: d must be heads * head_dim");
+    if (dp > 128) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: head_dim above 128 is not supported (head_pad must be 64, 96 or 128)");
+    if ((dp != 64 && dp != 96 && dp != 128) || hd > dp)
+        return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: head_pad must be 64, 96 or 128 and >= head_dim (the packer zero-pads every head)");
+    if (dp != 64 && c->q_prescaled) return visrep_set_error(VISREP_ERR_ARG, "vit_forward: pre-scaled Q (q_prescaled != 0) is built for head_pad 64");
+    if (c->d % 128 || c->mlp % 128 || c->kpad % 64)
+        return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: d, mlp % 128 and kpad % 64 required (mlp = the zero-padded MLP width)");
     const int grid = c->image_size / c->patch;
     if (grid * grid + (c->has_cls ? 1 : 0) != c->tokens) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: tokens != grid^2 + cls");
     hipStream_t s = (hipStream_t)stream;
@@ -317,6 +327,7 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
     bf16_t* vcls = (bf16_t*)(base + L.vcls);
     bf16_t* mlp = (bf16_t*)(base + L.mlp);
     const int d = c->d, T = c->tokens, P = grid * grid, M = B * T;
+    const int da = c->heads * dp;                         // width of Q, of K, of V and of the attention output (== d when dp == 64 == head_dim)
 
     // ---- embeddings: conv(k = s = patch) as im2col + GEMM with fused (bias, position add, CLS row skip)
     VR_TRY(visrep_im2col(pixels, pixel_dtype, mlp, B, c->image_size, c->image_size, c->patch, c->kpad, stream));
@@ -329,16 +340,16 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
     if (c->pre_ln) VR_TRY(visrep_layernorm(x, d, w->pre_ln_g, w->pre_ln_b, x, d, M, d, c->eps, stream));
 
     // V^T columns past B*T are read (with zero softmax weight) by the last key tile: keep them finite
-    if (hipMemsetAsync(vt, 0, (size_t)d * L.ldvt * 2, s) != hipSuccess) return visrep_set_error(VISREP_ERR_LAUNCH, "vit_forward: memset failed");
+    if (hipMemsetAsync(vt, 0, (size_t)da * L.ldvt * 2, s) != hipSuccess) return visrep_set_error(VISREP_ERR_LAUNCH, "vit_forward: memset failed");
 
     float2* rt = (float2*)(base + L.rt);
     if (hipMemsetAsync(rt, 0, (up(M, 128) + 8) * sizeof(float2), s) != hipSuccess) return visrep_set_error(VISREP_ERR_LAUNCH, "vit_forward: memset failed");
 
     float2* part = (float2*)(base + L.part);
-    const float scale = c->q_prescaled ? 0.f : 0.125f;   // head_dim^-0.5, head_dim = 64; 0 = folded into the Q weights (attn_fwd PS)
+    const float scale = c->q_prescaled ? 0.f : 1.f / sqrtf((float)hd);   // the TRUE head_dim^-0.5 (64: 0.125 exactly); 0 = folded into the Q weights (attn_fwd PS)
     // Image-aligned attention (attn_fwd_cls): the patch tokens of an image are whole key tiles and the CLS key is a side term, so V is
     // projected by two row-mapped GEMMs - the patch rows into V^T (column b (T - 1) + t - 1), the CLS rows into vcls [B, d]
-    const bool aligned = c->q_prescaled >= 2 && c->has_cls && visrep_mhsa_cls_supported(T) && t_visrep_attn_variant == 1;
+    const bool aligned = c->q_prescaled >= 2 && dp == 64 && hd == 64 && c->has_cls && visrep_mhsa_cls_supported(T) && t_visrep_attn_variant == 1;
     bool rt_ready = false;        // rt already holds the statistics of x (left by the previous layer's fc2 GEMM)
     for (int l = 0; l < n_layers; ++l) {
         const visrep_vit_layer& W = w->layers[l];
@@ -354,11 +365,11 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
         }
         a.lda = d; a.K = d; a.M = M;
         // Q | K projection
-        a.W = (const bf16_t*)W.wqkv; a.ldw = d; a.N = 2 * d; a.C = qk; a.ldc = 2 * d; a.bias = W.bqkv; a.epi = EPI_BIAS;
+        a.W = (const bf16_t*)W.wqkv; a.ldw = d; a.N = 2 * da; a.C = qk; a.ldc = 2 * da; a.bias = W.bqkv; a.epi = EPI_BIAS;
         VR_TRY(visrep_gemm_dispatch(a, s));
         // V projection written transposed + perm16 for the attention kernel
-        a.W = (const bf16_t*)W.wqkv + (size_t)2 * d * d; a.N = d; a.C = vt; a.ldc = L.ldvt; a.bias = W.bqkv + 2 * d; a.epi = EPI_VT;
-        if (fold) a.ln_s = W.sqkv + 2 * d;
+        a.W = (const bf16_t*)W.wqkv + (size_t)2 * da * d; a.N = da; a.C = vt; a.ldc = L.ldvt; a.bias = W.bqkv + 2 * da; a.epi = EPI_VT;
+        if (fold) a.ln_s = W.sqkv + 2 * da;
         if (aligned) {
             GemmArgs v = a;
             v.M = B * (T - 1); v.a_period = T - 1; v.a_stride = T; v.a_first = 1;
@@ -368,10 +379,10 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
             VR_TRY(visrep_mhsa_cls_fwd(qk, 2 * d, vt, L.ldvt, vcls, d, h, d, B, T, c->heads, 64, stream));
         } else {
             VR_TRY(visrep_gemm_dispatch(a, s));
-            VR_TRY(visrep_mhsa_fwd(qk, 2 * d, vt, L.ldvt, h, d, B, T, c->heads, 64, scale, stream));
+            VR_TRY(visrep_mhsa_fwd(qk, 2 * da, vt, L.ldvt, h, da, B, T, c->heads, dp, scale, stream));
         }
         // out projection + LayerScale + residual (in place on x)
-        a.A = h; a.ln_rt = nullptr; a.ln_s = nullptr;
+        a.A = h; a.lda = da; a.K = da; a.ldw = da; a.ln_rt = nullptr; a.ln_s = nullptr;
         a.W = (const bf16_t*)W.wo; a.N = d; a.C = x; a.ldc = d; a.bias = W.bo; a.epi = EPI_RESID; a.resid = x; a.ls = W.ls1;
         if (fold) { a.stat_rt = rt; a.stat_partial = part; a.stat_eps = c->eps; }   // LN2's statistics come out of this GEMM
         VR_TRY(visrep_gemm_dispatch(a, s));

@@ -17,6 +17,47 @@ def _round_up(v: int, a: int) -> int:
     return (v + a - 1) // a * a
 
 
+def head_pad_for(head_dim: int) -> int:
+    """Width a head occupies in the bf16 engine's buffers: 64, 96 (true widths 65 .. 96: attn_fwd96) or 128 (97 .. 128: attn_fwd<2>)."""
+    if head_dim < 64 or head_dim > 128:
+        raise ValueError("HIP attention kernel supports head_dim 64 .. 128 only (narrower and wider heads: the fp32 engine)")
+    return 64 if head_dim == 64 else 96 if head_dim <= 96 else 128
+
+
+def pad_tower_weights(spec: ViTSpec, layer: dict, dp: int, mp: int) -> dict:
+    """One layer's matrices with every head zero-padded from d / heads to `dp` lanes and the MLP from spec.mlp to `mp` units (host, fp32).
+    wqkv [3d, d] -> [3 heads dp, d] (the q, k and v rows of head h at h dp inside their block), bqkv likewise, wo [d, d] -> [d, heads dp]
+    (columns), w1 / b1 rows and w2 columns -> mp.  All padding is zeros, so nothing changes in exact arithmetic: a padded Q or K lane adds
+    0 * 0 to every score, a padded V lane is an output lane that meets a zero wo column, a padded MLP unit has zero weight and bias
+    (every activation here maps 0 to 0) and meets a zero w2 column."""
+    H, d, m = spec.heads, spec.d, spec.mlp
+    dh = d // H
+    L = dict(layer)
+    if dp != dh:
+        def rows(t):                                   # [3 d, ...] -> [3 H dp, ...]
+            t = t.detach().float()
+            out = torch.zeros((3, H, dp) + tuple(t.shape[1:]))
+            out[:, :, :dh] = t.reshape((3, H, dh) + tuple(t.shape[1:]))
+            return out.reshape((3 * H * dp,) + tuple(t.shape[1:]))
+        L["wqkv"] = rows(L["wqkv"])
+        if L.get("bqkv") is not None:
+            L["bqkv"] = rows(L["bqkv"])
+        wo = torch.zeros(d, H, dp)
+        wo[:, :, :dh] = L["wo"].detach().float().reshape(d, H, dh)
+        L["wo"] = wo.reshape(d, H * dp)
+    if mp != m:
+        w1 = torch.zeros(mp, d)
+        w1[:m] = L["w1"].detach().float()
+        w2 = torch.zeros(d, mp)
+        w2[:, :m] = L["w2"].detach().float()
+        L["w1"], L["w2"] = w1, w2
+        if L.get("b1") is not None:
+            b1 = torch.zeros(mp)
+            b1[:m] = L["b1"].detach().float()
+            L["b1"] = b1
+    return L
+
+
 _SCRATCH = {}
 
 
@@ -42,8 +83,12 @@ class VitEngine:
     `output_hidden_states=True` convention the reference towers index with `select_layer`).
     """
 
-    def __init__(self, spec: ViTSpec, weights: dict, device: Optional[torch.device] = None, fuse_ln: Optional[bool] = None):
-        """fuse_ln (default on; VISREP_FUSE_LN=0 turns it off): fold every block's LayerNorm into the GEMMs that consume it -
+    def __init__(self, spec: ViTSpec, weights: dict, device: Optional[torch.device] = None, fuse_ln: Optional[bool] = None,
+                 head_pad: Optional[int] = None):
+        """head_pad: lanes per head in the device buffers, None = head_pad_for(d / heads) (64 -> 64, 65 .. 96 -> 96, 97 .. 128 -> 128);
+        128 for a head of 65 .. 96 is the route attn_fwd96 replaced (attn_fwd<2> on heads padded to 128), kept reachable for A/B runs.
+        The MLP width is padded to a multiple of 128 alike (pad_tower_weights).
+        fuse_ln (default on; VISREP_FUSE_LN=0 turns it off): fold every block's LayerNorm into the GEMMs that consume it -
         gamma into the weight rows, beta into the bias, the per-row mean / rstd into the GEMM epilogue (ln_rt / ln_s) - so the
         normalised activations are never written to HBM, and take the row statistics from the epilogue of the residual GEMM that
         produced the rows (visrep_gemm_bf16_resid_stats) - so LayerNorm never reads the residual stream either; only layer 0's
@@ -55,10 +100,16 @@ class VitEngine:
         self.fuse_ln = (os.environ.get("VISREP_FUSE_LN", "1") != "0") if fuse_ln is None else bool(fuse_ln)
         self.spec = spec
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
-        if spec.d != spec.heads * 64:
-            raise ValueError("HIP attention kernel supports head_dim 64 only")
-        if spec.d % 128 or spec.mlp % 128:
-            raise ValueError("d and mlp must be multiples of 128")
+        if spec.d % spec.heads:
+            raise ValueError("d must be a multiple of heads")
+        self.head_dim = spec.d // spec.heads
+        self.head_pad = head_pad_for(self.head_dim) if head_pad is None else int(head_pad)
+        if self.head_pad not in (64, 96, 128) or self.head_pad < self.head_dim or (self.head_dim == 64) != (self.head_pad == 64):
+            raise ValueError(f"head_pad must be 96 or 128 and >= the head width {self.head_dim} (64-wide heads are not padded)")
+        if spec.d % 128:
+            raise ValueError("d must be a multiple of 128")
+        self.mlp_pad = _round_up(spec.mlp, 128)
+        da = spec.heads * self.head_pad
         ensure_scratch(self.device)
         self.kpad = _round_up(3 * spec.patch * spec.patch, 64)
         self._keep = []          # device tensors referenced by raw pointers
@@ -88,11 +139,12 @@ class VitEngine:
         # softmax scale in the exponent's base, folded into the Q rows of the Q|K|V projection (attn_fwd PS): q' = c * q with
         # c = head_dim^-0.5 * log2(e), so that 2^(q'.k) = e^(q.k / sqrt(head_dim)).  VISREP_Q_PRESCALE=0 keeps the scale in the kernel.
         # VISREP_Q_PRESCALE=2 (default) additionally lets towers with a CLS token and 64 n patches run the image-aligned attention kernel.
-        self._q_mode = int(os.environ.get("VISREP_Q_PRESCALE", "2"))
+        # Padded heads (head_pad 96 / 128) keep the scale in the kernel: the pre-scaled variant of the flash kernel is built for width 64 only.
+        self._q_mode = int(os.environ.get("VISREP_Q_PRESCALE", "2")) if self.head_pad == 64 else 0
         self.q_prescaled = self._q_mode != 0
-        qc = torch.ones(3 * spec.d)
+        qc = torch.ones(3 * da)
         if self.q_prescaled:
-            qc[: spec.d] = 0.125 * 1.4426950408889634
+            qc[: da] = self.head_dim ** -0.5 * 1.4426950408889634
 
         def fold(Wm, bias, g, b, rowscale=None):
             """Linear(LayerNorm(x)) = rstd * (x (g o W)^T - mean * s) + (W b + bias): (g o W in bf16, s over the ROUNDED rows, b').
@@ -105,7 +157,7 @@ class VitEngine:
 
         for i, L in enumerate(weights["layers"]):
             ent = self._layers[i]
-            L = dict(L)
+            L = pad_tower_weights(spec, L, self.head_pad, self.mlp_pad)       # before the fold: it sees the padded matrices (zero rows: s = 0, b' = 0)
             extra = {"sqkv": None, "s1": None}
             if self.fuse_ln:
                 L["wqkv"], extra["sqkv"], L["bqkv"] = fold(L["wqkv"], L.get("bqkv"), L["ln1_g"], L["ln1_b"], qc)
@@ -127,8 +179,9 @@ class VitEngine:
         for k, v in self._vecs.items():
             setattr(self._w, k, 0 if v is None else v.data_ptr())
         self._w.layers = C.cast(self._layers, C.POINTER(_lib.VitLayer))
-        self._cfg = _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, spec.mlp, n, spec.tokens,
-                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), self._q_mode)
+        self._cfg = _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, self.mlp_pad, n, spec.tokens,
+                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), self._q_mode,
+                                   self.head_dim, self.head_pad)
         self._ws: Dict[int, torch.Tensor] = {}
         self._pinned = set()                 # batch sizes whose workspace a captured HIP graph refers to
 
@@ -549,10 +602,11 @@ def layernorm(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float) -> 
     return y
 
 
-def mhsa(qk: torch.Tensor, vt: torch.Tensor, B: int, T: int, H: int, scale: float) -> torch.Tensor:
+def mhsa(qk: torch.Tensor, vt: torch.Tensor, B: int, T: int, H: int, scale: float, head_dim: int = 64) -> torch.Tensor:
+    """qk [B T, 2 H head_dim] (Q | K), vt [H head_dim, ldvt]; head_dim = the padded width of the buffers (64, 96 or 128)."""
     lib = _lib.require_gpu()
-    out = torch.empty(B * T, H * 64, dtype=torch.bfloat16, device=qk.device)
-    rc = lib.visrep_mhsa_fwd(_lib.ptr(qk), qk.stride(0), _lib.ptr(vt), vt.stride(0), _lib.ptr(out), out.stride(0), B, T, H, 64,
+    out = torch.empty(B * T, H * head_dim, dtype=torch.bfloat16, device=qk.device)
+    rc = lib.visrep_mhsa_fwd(_lib.ptr(qk), qk.stride(0), _lib.ptr(vt), vt.stride(0), _lib.ptr(out), out.stride(0), B, T, H, head_dim,
                              scale, _lib.stream_ptr())
     _lib.check(rc, "visrep_mhsa_fwd")
     return out

@@ -67,6 +67,13 @@ SPECS: Dict[str, ViTSpec] = {
                                      "gelu", 1e-6, True, False, True, True, "dinov2", pos_grid=37),
     "google/siglip-base-patch16-224": ViTSpec("google/siglip-base-patch16-224", 224, 16, 768, 12, 12, 3072,
                                               "gelu_tanh", 1e-6, False, False, True, False, "siglip"),
+    # Heads that are not 64 wide (16 x 72, 16 x 80; the bf16 engine pads them to 96, the MLP of so400m from 4304 to 4352).  Not in the
+    # reference registry: users add the id to llava_arch.build_function_mapping.  Shapes as recalled from the public HF configs - they could
+    # not be read offline; a local checkpoint's config.json always wins (HipViTTower._spec_and_weights).
+    "google/siglip-so400m-patch14-384": ViTSpec("google/siglip-so400m-patch14-384", 384, 14, 1152, 27, 16, 4304,
+                                                "gelu_tanh", 1e-6, False, False, True, False, "siglip"),
+    "laion/CLIP-ViT-H-14-laion2B-s32B-b79K": ViTSpec("laion/CLIP-ViT-H-14-laion2B-s32B-b79K", 224, 14, 1280, 32, 16,
+                                                     5120, "gelu", 1e-5, True, True, False, False, "clip"),
 }
 
 
