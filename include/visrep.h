@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define VISREP_VERSION 620   /* 620: head widths other than 64 in the bf16 tower - visrep_vit_config grows head_dim / head_pad (struct change), visrep_mhsa_fwd takes head_dim 64 | 96 | 128, visrep_attention_fwd head_dim 96, route id 12; visrep_im2col and visrep_vit_forward_cpu no longer refuse an image side that is not a multiple of the patch - they floor the division as Conv2d does (newly accepted argument values).  610: visrep_cscore_transfer_packed2 / visrep_cscore_transfer2_cpu, the key-point transfer on two per-encoder banks (new exports only).  600 = round 6: reserved CUs, GEMM tile-walk knob, gemm variants 6-8, visrep_masked_nn_min_f32, window < 0 in the C-score transfers (new exports / newly accepted argument values only).  500 = round 5: device CU count, routing counters, MFMA probe, A-score reference arithmetic, host twins (new exports only).  410 = round 4: split-route `products`, stream-keyed scratch, per-thread knobs (changed signatures); 410: q_prescaled = 2, row-mapped GEMM, image-aligned / wide-head attention, conv + GroupNorm partials */
+#define VISREP_VERSION 630   /* 630: SwiGLU-FFN towers (DINOv2-giant) - VISREP_ACT_SWIGLU = 4 in visrep_vit_config::act (w1 / b1 / s1 then have 2 * mlp rows), VISREP_EPI_GATED, visrep_gemm_bf16_gated, visrep_swiglu, visrep_swiglu_f32, visrep_set_fuse_gate, visrep_debug_gated_refusal (new exports / newly accepted argument values; no struct layout change).  620: head widths other than 64 in the bf16 tower - visrep_vit_config grows head_dim / head_pad (struct change), visrep_mhsa_fwd takes head_dim 64 | 96 | 128, visrep_attention_fwd head_dim 96, route id 12; visrep_im2col and visrep_vit_forward_cpu no longer refuse an image side that is not a multiple of the patch - they floor the division as Conv2d does (newly accepted argument values).  610: visrep_cscore_transfer_packed2 / visrep_cscore_transfer2_cpu, the key-point transfer on two per-encoder banks (new exports only).  600 = round 6: reserved CUs, GEMM tile-walk knob, gemm variants 6-8, visrep_masked_nn_min_f32, window < 0 in the C-score transfers (new exports / newly accepted argument values only).  500 = round 5: device CU count, routing counters, MFMA probe, A-score reference arithmetic, host twins (new exports only).  410 = round 4: split-route `products`, stream-keyed scratch, per-thread knobs (changed signatures); 410: q_prescaled = 2, row-mapped GEMM, image-aligned / wide-head attention, conv + GroupNorm partials */
 
 enum { VISREP_BF16 = 0, VISREP_F32 = 1 };
 enum { VISREP_OK = 0, VISREP_ERR_ARG = -1, VISREP_ERR_SHAPE = -2, VISREP_ERR_LAUNCH = -3 };
@@ -31,9 +31,15 @@ enum {
     VISREP_EPI_RESID = 2,  /* C = resid + ls * (A W^T + bias)                    (Linear + LayerScale + add)    */
     VISREP_EPI_VT = 3,     /* V^T scatter for visrep_mhsa_fwd (see below)                                        */
     VISREP_EPI_PATCH = 4,  /* patch-embed: row remap past the CLS row + position add                             */
-    VISREP_EPI_F32 = 5     /* C(fp32) = A W^T + bias                                                             */
+    VISREP_EPI_F32 = 5,    /* C(fp32) = A W^T + bias                                                             */
+    VISREP_EPI_GATED = 7   /* C[m, 16 t + r] = silu(g) * u over N / 2 columns (visrep_gemm_bf16_gated only; 6 is internal) */
 };
-enum { VISREP_ACT_NONE = 0, VISREP_ACT_QUICK_GELU = 1, VISREP_ACT_GELU_ERF = 2, VISREP_ACT_GELU_TANH = 3 };
+enum { VISREP_ACT_NONE = 0, VISREP_ACT_QUICK_GELU = 1, VISREP_ACT_GELU_ERF = 2, VISREP_ACT_GELU_TANH = 3,
+       /* visrep_vit_config::act only (not an element-wise activation of the GEMM entry points): the tower's MLP is HF Dinov2SwiGLUFFN,
+        * weights_out(silu(x1) * x2) with x1, x2 = weights_in(x).chunk(2).  `mlp` is then the (padded) hidden width h and w1 / b1 / s1 have 2 * mlp
+        * rows: for visrep_vit_forward in the 16-row interleave of visrep_gemm_bf16_gated (or, with visrep_set_fuse_gate(0), in HF chunk order);
+        * for the fp32 and host towers in HF chunk order (gate rows, then value rows).  w2 is [d, mlp]. */
+       VISREP_ACT_SWIGLU = 4 };
 
 int visrep_version(void);
 /* copies the calling thread's last error message (NUL terminated) into buf; returns its length */
@@ -177,6 +183,25 @@ int visrep_gemm_bf16_rows(const void* A, int lda, int row_period, int row_stride
                           const void* ln_rt, const float* ln_s, void* C, int ldc, int M, int N, int K, int epilogue, int act, void* stream);
 int visrep_gemm_bf16_resid_stats(const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc, int M, int N, int K,
                                  const void* resid, const float* ls, void* rt, void* partial, float eps, void* stream);
+/* ---- Gated (SwiGLU) GEMM: the GEMM has N = 2 mp columns, the output C [M, mp] (ldc >= mp) bf16:
+ *   C[m, 16 t + r] = bf16( silu(g) * u ),  g = (A W^T + bias)[m, 32 t + r],  u = (A W^T + bias)[m, 32 t + 16 + r],  r < 16
+ * (g and u in fp32, one rounding).  So row 32 t + r of W / bias / ln_s is the GATE row (HF x1) of hidden unit 16 t + r and row 32 t + 16 + r
+ * its VALUE row (x2): the packer interleaves the two halves of Dinov2SwiGLUFFN.weights_in in blocks of 16 rows, which puts both operands of
+ * an output element into the same lane of the MFMA accumulators.  ln_rt / ln_s (both or neither): LayerNorm folded as in visrep_gemm_bf16_ln.
+ * N % 128 == 0 (mp % 64), K % 64 == 0.  No row map, convolution, row statistics or residual; few-tile problems are not split along K. */
+int visrep_gemm_bf16_gated(const void* A, int lda, const void* W, int ldw, const float* bias, const void* ln_rt, const float* ln_s, void* C,
+                           int ldc, int M, int N, int K, void* stream);
+/* The unfused pair in HF chunk order: y[m, f] = silu(x[m, f]) * x[m, F + f], x [M, 2 F] (ldx), y [M, F] (ldy).  bf16: F, ldx, ldy % 8 == 0;
+ * fp32: % 4 (libm expf, as the fp32 towers' activations).  What the fp32 towers and the A/B baseline of the gated epilogue run. */
+int visrep_swiglu(const void* x, int ldx, void* y, int ldy, long M, int F, void* stream);
+int visrep_swiglu_f32(const float* x, int ldx, float* y, int ldy, long M, int F, void* stream);
+/* Per-thread A/B knob: 1 (default) = visrep_vit_forward runs a SwiGLU tower's fc1 as visrep_gemm_bf16_gated (interleaved w1); 0 = as a plain
+ * GEMM + visrep_swiglu (w1 / b1 / s1 in HF chunk order; visrep_vit_workspace_bytes grows by the [M, 2 mlp] intermediate - query it with the
+ * knob already set).  Returns the previous value. */
+int visrep_set_fuse_gate(int on);
+/* Tests: hands the GEMM dispatcher a gated problem combined with 1 = a convolution, 2 = an A row map, 3 = row statistics, 4 = GroupNorm
+ * partials (placeholder pointers - every one of them must be refused before any launch) and returns the dispatcher's code. */
+int visrep_debug_gated_refusal(int which);
 
 /* ---- multi-head self-attention forward (HF CLIPAttention / Dinov2SelfAttention / SiglipAttention: softmax(QK^T
  * scale) V, fp32 softmax).  qk: [B*T, 2*H*head_dim] bf16 (Q | K, head-major columns: K starts at column H*head_dim); vt: V^T as written by

@@ -11,10 +11,11 @@ import threading
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VISREP_LIB") or os.path.join(_PKG, "libvisrep_hip.so")   # VISREP_LIB: diagnostic builds only
 
-ABI_VERSION = 620                 # include/visrep.h VISREP_VERSION this binding was written against (checked at load)
+ABI_VERSION = 630                 # include/visrep.h VISREP_VERSION this binding was written against (checked at load)
 BF16, F32 = 0, 1
 EPI_BIAS, EPI_ACT, EPI_RESID, EPI_VT, EPI_PATCH, EPI_F32 = range(6)
-ACT = {"none": 0, "quick_gelu": 1, "gelu": 2, "gelu_erf": 2, "gelu_tanh": 3, "gelu_pytorch_tanh": 3}
+EPI_GATED = 7
+ACT = {"none": 0, "quick_gelu": 1, "gelu": 2, "gelu_erf": 2, "gelu_tanh": 3, "gelu_pytorch_tanh": 3, "swiglu": 4}
 
 
 class VitConfig(C.Structure):
@@ -61,6 +62,11 @@ SIGNATURES = {
     "visrep_gemm_bf16_ln": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "visrep_gemm_bf16_rows": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "visrep_gemm_bf16_resid_stats": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp]),
+    "visrep_gemm_bf16_gated": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "visrep_swiglu": (_i, [_vp, _i, _vp, _i, _l, _i, _vp]),
+    "visrep_swiglu_f32": (_i, [_vp, _i, _vp, _i, _l, _i, _vp]),
+    "visrep_set_fuse_gate": (_i, [_i]),
+    "visrep_debug_gated_refusal": (_i, [_i]),
     "visrep_attention_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "visrep_groupnorm_workspace_bytes": (_sz, [_i, _i, _i]),
     "visrep_groupnorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),

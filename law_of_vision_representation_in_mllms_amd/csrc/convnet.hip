@@ -220,6 +220,28 @@ __global__ __launch_bounds__(256) void geglu(const bf16_t* __restrict__ x, bf16_
     *reinterpret_cast<u32x4*>(y + row * ldy + f0) = o;
 }
 
+// ------------------------------------------------------------------------------------------------ SwiGLU (HF chunk order: gate | value)
+// The unfused twin of the GEMMs' gated epilogue (A/B baseline, VISREP_FUSE_GATE=0): silu with the same v_exp / v_rcp arithmetic, but on
+// operands that were already rounded to bf16 once.
+__global__ __launch_bounds__(256) void swiglu(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, long total_vec, int F, int ldx, int ldy) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total_vec) return;
+    const int fv = F >> 3;
+    const long row = idx / fv;
+    const int f0 = (int)(idx - row * fv) * 8;
+    const u32x4 g = *reinterpret_cast<const u32x4*>(x + row * ldx + f0);
+    const u32x4 u = *reinterpret_cast<const u32x4*>(x + row * ldx + F + f0);
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float g0 = bf_lo(g[e]), g1 = bf_hi(g[e]);
+        const float s0 = g0 * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g0));
+        const float s1 = g1 * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g1));
+        o[e] = pack_bf16(s0 * bf_lo(u[e]), s1 * bf_hi(u[e]));
+    }
+    *reinterpret_cast<u32x4*>(y + row * ldy + f0) = o;
+}
+
 // ------------------------------------------------------------------------------------------------ row softmax (fp32 -> bf16)
 __global__ __launch_bounds__(256) void softmax_rows(const float* __restrict__ s, bf16_t* __restrict__ pr, int n, int lds_, int ldp, float scale) {
     __shared__ float red[4];
@@ -452,6 +474,15 @@ extern "C" int visrep_geglu(const void* x, int ldx, void* y, int ldy, long M, in
     const long total = M * (F / 8);
     hipLaunchKernelGGL(geglu, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, total, F, ldx, ldy);
     return launched("geglu: launch failed");
+}
+
+extern "C" int visrep_swiglu(const void* x, int ldx, void* y, int ldy, long M, int F, void* stream) {
+    if (!x || !y) return visrep_set_error(VISREP_ERR_ARG, "swiglu: null pointer");
+    if (M <= 0 || F <= 0 || F % 8 || ldx % 8 || ldy % 8 || ldx < 2 * F || ldy < F || ((uintptr_t)x & 15) || ((uintptr_t)y & 15))
+        return visrep_set_error(VISREP_ERR_SHAPE, "swiglu: F and leading dimensions must be multiples of 8, ldx >= 2 F, ldy >= F, 16-byte aligned pointers");
+    const long total = M * (F / 8);
+    hipLaunchKernelGGL(swiglu, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, total, F, ldx, ldy);
+    return launched("swiglu: launch failed");
 }
 
 extern "C" int visrep_softmax_rows(const float* scores, int lds_, void* probs, int ldp, int rows, int n, float scale, void* stream) {

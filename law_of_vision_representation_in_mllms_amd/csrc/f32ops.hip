@@ -759,6 +759,39 @@ int launch_gemm_f32(const GemmF32Args& a, int nb, hipStream_t s) {
 }
 
 inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+// SwiGLU in fp32, HF chunk order (x [M, 2 F]: gate | value), libm expf like the other exact activations here.  y fp32 [M, F] and / or the
+// bf16 planes of the result [M, NPL F] (the split route's fc2 operand); NPL = 0: no planes.
+template <int NPL>
+__global__ __launch_bounds__(256) void swiglu_f32_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy, bf16_t* __restrict__ planes,
+                                                         long total_vec, int F) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total_vec) return;
+    const int fv = F >> 2;
+    const long row = idx / fv;
+    const int f0 = (int)(idx - row * fv) * 4;
+    const float4 g = *reinterpret_cast<const float4*>(x + row * ldx + f0);
+    const float4 u = *reinterpret_cast<const float4*>(x + row * ldx + F + f0);
+    const float v[4] = {g.x / (1.0f + expf(-g.x)) * u.x, g.y / (1.0f + expf(-g.y)) * u.y, g.z / (1.0f + expf(-g.z)) * u.z, g.w / (1.0f + expf(-g.w)) * u.w};
+    if (y) *reinterpret_cast<float4*>(y + row * ldy + f0) = float4{v[0], v[1], v[2], v[3]};
+    if (NPL > 0) {
+        u32x2 hi, mid, lo;
+        split3(v, hi, mid, lo);
+        bf16_t* pr = planes + row * (long)(NPL * F) + f0;
+        *reinterpret_cast<u32x2*>(pr) = hi;
+        *reinterpret_cast<u32x2*>(pr + F) = mid;
+        if (NPL == 3) *reinterpret_cast<u32x2*>(pr + 2 * F) = lo;
+    }
+}
+int launch_swiglu_f32(const float* x, int ldx, float* y, int ldy, bf16_t* planes, int npl, long M, int F, hipStream_t s) {
+    const long total = M * (F / 4);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (npl == 3) hipLaunchKernelGGL(swiglu_f32_kernel<3>, grid, dim3(256), 0, s, x, ldx, y, ldy, planes, total, F);
+    else if (npl == 2) hipLaunchKernelGGL(swiglu_f32_kernel<2>, grid, dim3(256), 0, s, x, ldx, y, ldy, planes, total, F);
+    else hipLaunchKernelGGL(swiglu_f32_kernel<0>, grid, dim3(256), 0, s, x, ldx, y, ldy, planes, total, F);
+    return hipGetLastError() == hipSuccess ? 0 : visrep_set_error(VISREP_ERR_LAUNCH, "swiglu_f32: launch failed");
+}
+inline bool is_swiglu(const visrep_vit_config* c) { return c->act == VISREP_ACT_SWIGLU; }
 struct WsF32 { size_t h, qkv, sc, mlp, total; int lds; };
 WsF32 layout_f32(const visrep_vit_config* c, int B) {
     WsF32 w;
@@ -768,7 +801,7 @@ WsF32 layout_f32(const visrep_vit_config* c, int B) {
     w.h = off;   off += up256(M * c->d * 4);
     w.qkv = off; off += up256(M * 3 * c->d * 4);
     w.sc = off;  off += up256((size_t)B * c->heads * c->tokens * w.lds * 4);
-    const size_t mlp_b = M * c->mlp * 4;
+    const size_t mlp_b = M * c->mlp * 4 * (is_swiglu(c) ? 3 : 1);          // SwiGLU: the hidden [M, mlp], then fc1's [M, 2 mlp] output
     const size_t P = (size_t)c->tokens - c->has_cls;
     const size_t emb_b = up256((size_t)B * P * c->kpad * 4) + (size_t)B * P * c->d * 4;    // im2col columns + patch rows alias the MLP buffer
     w.mlp = off; off += up256(mlp_b > emb_b ? mlp_b : emb_b);
@@ -785,7 +818,7 @@ WsF32X layout_f32x(const visrep_vit_config* c, int B) {
     size_t off = 0;
     w.hp = off;  off += up256(M * 3 * c->d * 2);
     w.qkv = off; off += up256(M * 3 * c->d * 4);
-    const size_t mlp_b = M * 3 * c->mlp * 2;
+    const size_t mlp_b = M * 3 * c->mlp * 2 + (is_swiglu(c) ? M * 2 * c->mlp * 4 : 0);   // SwiGLU: fc1's fp32 [M, 2 mlp] output behind the planes
     const size_t P = (size_t)c->tokens - c->has_cls;
     const size_t emb_b = up256((size_t)B * P * c->kpad * 4) + (size_t)B * P * c->d * 4;
     w.mlpp = off; off += up256(mlp_b > emb_b ? mlp_b : emb_b);
@@ -833,6 +866,13 @@ extern "C" int visrep_gemm_f32_split(const void* a_planes, const void* w_planes,
     if (C && (ldc < N || (ldc & 3))) return visrep_set_error(VISREP_ERR_SHAPE, "gemm_f32_split: ldc >= N, % 4 == 0");
     return launch_gemm_split((const bf16_t*)a_planes, (const bf16_t*)w_planes, M, N, K, products, bias, act, resid, ls, C, C ? ldc : N,
                              (bf16_t*)out_planes, (hipStream_t)stream);
+}
+
+extern "C" int visrep_swiglu_f32(const float* x, int ldx, float* y, int ldy, long M, int F, void* stream) {
+    if (!x || !y) return visrep_set_error(VISREP_ERR_ARG, "swiglu_f32: null pointer");
+    if (M <= 0 || F <= 0 || (F & 3) || (ldx & 3) || (ldy & 3) || ldx < 2 * F || ldy < F || ((uintptr_t)x & 15) || ((uintptr_t)y & 15))
+        return visrep_set_error(VISREP_ERR_SHAPE, "swiglu_f32: F and leading dimensions must be multiples of 4, ldx >= 2 F, ldy >= F, 16-byte aligned pointers");
+    return launch_swiglu_f32(x, ldx, y, ldy, nullptr, 0, M, F, (hipStream_t)stream);
 }
 
 extern "C" int visrep_debug_f32_attention(int mask) {          // per-thread diagnostic, see t_visrep_f32_attention_dbg; returns the previous mask
@@ -971,6 +1011,12 @@ extern "C" int visrep_vit_forward_f32(const visrep_vit_config* c, const visrep_v
         GemmF32Args f{};
         f.alpha = 1.f; f.nb2 = 1;
         f.A = h; f.lda = d; f.K = d; f.M = M; f.W = (const float*)W.w1; f.ldw = d; f.N = c->mlp; f.C = mlp; f.ldc = c->mlp; f.bias = W.b1; f.epi = EPI_ACT; f.act = c->act;
+        if (is_swiglu(c)) {                                   // Dinov2SwiGLUFFN: w1 [2 mlp, d] in HF chunk order; plain GEMM, then the element-wise gate
+            float* gu = mlp + (size_t)M * c->mlp;
+            f.N = 2 * c->mlp; f.C = gu; f.ldc = 2 * c->mlp; f.epi = EPI_BIAS; f.act = 0;
+            VR_TRY(launch_gemm_f32(f, 1, s));
+            VR_TRY(launch_swiglu_f32(gu, 2 * c->mlp, mlp, c->mlp, nullptr, 0, M, c->mlp, s));
+        } else
         VR_TRY(launch_gemm_f32(f, 1, s));
         f.A = mlp; f.lda = c->mlp; f.K = c->mlp; f.W = (const float*)W.w2; f.ldw = c->mlp; f.N = d; f.C = x; f.ldc = d; f.bias = W.b2; f.epi = EPI_RESID; f.act = 0;
         f.resid = x; f.ls = W.ls2;
@@ -1038,6 +1084,11 @@ extern "C" int visrep_vit_forward_f32_split(const visrep_vit_config* c, const vi
         if (hipGetLastError() != hipSuccess) return visrep_set_error(VISREP_ERR_LAUNCH, "vit_forward_f32_split: attention launch failed");
         VR_TRY(launch_gemm_split(hp, (const bf16_t*)S.wo, M, d, d, products, W.bo, ACT_NONE, x, W.ls1, x, d, nullptr, s));
         VR_TRY(ln_split(W.ln2_g, W.ln2_b));
+        if (is_swiglu(c)) {                                   // fp32 [M, 2 mlp] out of the GEMM, the gate writes the hidden's planes
+            float* gu = (float*)(mlpp + (size_t)M * 3 * c->mlp);
+            VR_TRY(launch_gemm_split(hp, (const bf16_t*)S.w1, M, 2 * c->mlp, d, products, W.b1, ACT_NONE, nullptr, nullptr, gu, 2 * c->mlp, nullptr, s));
+            VR_TRY(launch_swiglu_f32(gu, 2 * c->mlp, nullptr, 0, mlpp, npl, M, c->mlp, s));
+        } else
         VR_TRY(launch_gemm_split(hp, (const bf16_t*)S.w1, M, c->mlp, d, products, W.b1, c->act, nullptr, nullptr, nullptr, c->mlp, mlpp, s));
         VR_TRY(launch_gemm_split(mlpp, (const bf16_t*)S.w2, M, d, c->mlp, products, W.b2, ACT_NONE, x, W.ls2, x, d, nullptr, s));
     }

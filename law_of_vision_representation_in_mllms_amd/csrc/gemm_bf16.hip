@@ -144,7 +144,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_128(const GemmArgs p) {
         return;
     }
     if constexpr (GN) { gemm_epilogue_rowmajor_gn<EPI, 4, 4>(p, acc, m0 + wm * 64, n0 + wn * 64, fr, fg); return; }
-    if (EPI == EPI_VT) gemm_epilogue_vt<4, 4>(p, acc, m0 + wm * 64, n0 + wn * 64, fr, fg);
+    if constexpr (EPI == EPI_GATED) gemm_epilogue_gated<4, 4>(p, acc, m0 + wm * 64, n0 + wn * 64, fr, fg);
+    else if (EPI == EPI_VT) gemm_epilogue_vt<4, 4>(p, acc, m0 + wm * 64, n0 + wn * 64, fr, fg);
     else gemm_epilogue_rowmajor<EPI, 4, 4>(p, acc, m0 + wm * 64, n0 + wn * 64, fr, fg);
 }
 
@@ -330,7 +331,7 @@ namespace {
 // variant 6: the duo kernel (gemm_bf16_duo.hip: two independent 4-wave workgroups per CU, 256 x 128 tiles) wherever it supports the problem;
 // variant 7: for N <= 1024 only (out-proj, fc2, V^T: the shapes whose epilogue is the largest share of a tile).  Everything else as variant 5.
 bool duo_wanted(const GemmArgs& a, int variant) {
-    return variant >= 6 && visrep_gemm_duo_supports(a) && !a.gn_partial && a.a_period <= 0 && (variant != 7 || a.N <= 1024);
+    return variant >= 6 && a.epi != EPI_GATED && visrep_gemm_duo_supports(a) && !a.gn_partial && a.a_period <= 0 && (variant != 7 || a.N <= 1024);
 }
 int dispatch_one(const GemmArgs& a, hipStream_t s, int variant) {
     if (duo_wanted(a, variant)) {
@@ -386,6 +387,7 @@ int dispatch_one(const GemmArgs& a, hipStream_t s, int variant) {
         case EPI_VT: return launch<EPI_VT>(a, s);
         case EPI_PATCH: return launch<EPI_PATCH>(a, s);
         case EPI_F32: return launch<EPI_F32>(a, s);
+        case EPI_GATED: return launch<EPI_GATED>(a, s);
     }
     return visrep_set_error(VISREP_ERR_ARG, "gemm: unknown epilogue");
 }
@@ -400,6 +402,7 @@ namespace {
 // fused.  Returns 1 when the problem was handled this way, 0 when it was not eligible, < 0 on error.
 int try_split_k(const GemmArgs& a, hipStream_t s) {
     if (!(a.epi != EPI_PATCH && a.K >= 1024 && (a.N & 3) == 0) || a.gn_partial) return 0;     // GroupNorm partials come from a GEMM epilogue only
+    if (a.epi == EPI_GATED) return 0;                             // the reduction has no gate: few-tile gated problems run unsplit on the 128x128 kernel
     const VisrepScratch reg = visrep_scratch_for(s);               // the buffer of (this device, this stream), else the device-wide one
     void* const scratch = reg.ptr;
     const size_t scratch_bytes = reg.bytes;
@@ -474,6 +477,14 @@ int visrep_gemm_dispatch(const GemmArgs& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0) return visrep_set_error(VISREP_ERR_SHAPE, "gemm: empty problem");
     if (a.N % 64 != 0 || a.K % BK != 0) return visrep_set_error(VISREP_ERR_SHAPE, "gemm: N and K must be multiples of 64");
     if ((a.lda % 8) || (a.ldw % 8) || (a.ldc % 4)) return visrep_set_error(VISREP_ERR_SHAPE, "gemm: leading dimensions must keep 16-B row alignment");
+    if (a.epi == EPI_GATED) {                                     // N = 2 mp GEMM columns -> mp output columns (gemm_epilogue.h)
+        if (a.conv) return visrep_set_error(VISREP_ERR_ARG, "gemm: the gated epilogue does not serve convolutions");
+        if (a.a_period > 0) return visrep_set_error(VISREP_ERR_ARG, "gemm: the gated epilogue does not take an A row map");
+        if (a.stat_rt || a.stat_partial) return visrep_set_error(VISREP_ERR_ARG, "gemm: the gated epilogue does not emit row statistics");
+        if (a.gn_partial) return visrep_set_error(VISREP_ERR_ARG, "gemm: the gated epilogue does not emit GroupNorm partials");
+        if (a.N % 128 != 0 || a.ldc < a.N / 2) return visrep_set_error(VISREP_ERR_SHAPE, "gemm: gated epilogue needs N = 2 mp with mp % 64 == 0 and ldc >= mp");
+        if (a.resid || a.ls) return visrep_set_error(VISREP_ERR_ARG, "gemm: the gated epilogue takes no residual / LayerScale");
+    }
     if (a.stat_rt && a.epi != EPI_RESID) return visrep_set_error(VISREP_ERR_ARG, "gemm: row statistics are an EPI_RESID feature");
     if (a.a_period > 0 && (a.conv || a.epi == EPI_RESID || a.epi == EPI_PATCH || a.a_stride < a.a_period || a.a_first < 0))
         return visrep_set_error(VISREP_ERR_ARG, "gemm: the A row map serves plain BIAS / ACT / VT / F32 epilogues only");

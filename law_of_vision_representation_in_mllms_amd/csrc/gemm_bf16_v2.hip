@@ -275,7 +275,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_256(const GemmArgs p) {
                 kt = 0;
                 int m0, n0; tw.decode(ti, m0, n0); ++ti;
                 const int mb = m0 + grp * 128, nb = n0 + wn * 64;
-                if (EPI == EPI_VT) gemm_epilogue_vt<8, 4>(p, acc, mb, nb, fr, fg);
+                if constexpr (EPI == EPI_GATED) gemm_epilogue_gated<8, 4>(p, acc, mb, nb, fr, fg);
+                else if (EPI == EPI_VT) gemm_epilogue_vt<8, 4>(p, acc, mb, nb, fr, fg);
                 else gemm_epilogue_rowmajor<EPI, 8, 4, true>(p, acc, mb, nb, fr, fg);
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
@@ -319,6 +320,7 @@ int visrep_gemm_v2_dispatch(const GemmArgs& a, hipStream_t s) {
         case EPI_VT: return launch2<EPI_VT>(a, s);
         case EPI_PATCH: return launch2<EPI_PATCH>(a, s);
         case EPI_F32: return launch2<EPI_F32>(a, s);
+        case EPI_GATED: return launch2<EPI_GATED>(a, s);
     }
     return visrep_set_error(VISREP_ERR_ARG, "gemm: unknown epilogue");
 }

@@ -460,6 +460,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_256q(const GemmArgs p) {
 #endif
                 if constexpr (EPI == EPI_VT) gemm_epilogue_vt<8, 4>(p, acc, mb, nb, fr, hi);
                 else if constexpr (EPI == EPI_F32X) gemm_epilogue_f32x<8, 4>(p, acc, mb, nb, fr, hi);
+                else if constexpr (EPI == EPI_GATED) gemm_epilogue_gated<8, 4>(p, acc, mb, nb, fr, hi);
                 else {
                     if constexpr (GN_) gemm_gn_partials_prepass<8, 4, EPI == EPI_RESID>(p, acc, mb, nb, fr, hi);
                     gemm_epilogue_rowmajor<EPI, 8, 4, true>(p, acc, mb, nb, fr, hi);
@@ -671,6 +672,7 @@ int visrep_gemm_v5_dispatch(const GemmArgs& a, hipStream_t s) {
         case EPI_VT: return launch5<EPI_VT>(a, s);
         case EPI_F32: return launch5<EPI_F32>(a, s);
         case EPI_F32X: return launch5<EPI_F32X>(a, s);
+        case EPI_GATED: return launch5<EPI_GATED>(a, s);
     }
 #endif
     return visrep_set_error(VISREP_ERR_ARG, "gemm: unknown epilogue");

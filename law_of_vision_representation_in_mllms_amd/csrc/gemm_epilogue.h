@@ -420,6 +420,113 @@ VR_DEV void gemm_epilogue_rowmajor(const GemmArgs& p, const ACC (&acc)[NI][NJ], 
     }
 }
 
+// ---- EPI_GATED (SwiGLU fc1, HF Dinov2SwiGLUFFN): the GEMM has N = 2 mp columns, the output mp.  The packer interleaves the two halves of
+// the weight in blocks of 16 rows - GEMM column 32 t + r is the gate of hidden unit 16 t + r, column 32 t + 16 + r its value (r < 16) - so that
+// with 16x16 accumulators the two operands of an output element are acc[i][2 t][e] and acc[i][2 t + 1][e] of the SAME lane (with 32x32
+// accumulators they would be registers 4 q + e and 4 (q + 2) + e; no product kernel has those, hence the static_assert):
+//   C[m, 16 t + 4 hg + e] = bf16( silu(g) * u ),  g / u = fp32 accumulator + bias (after the optional LayerNorm fold), one rounding.
+// No cross-lane traffic for the gate, a lane still owns four consecutive OUTPUT columns per block (8-byte stores), and the WIDE pairing of
+// the row-major epilogue applies per pair of output blocks.  A wave tile of NJ * 16 GEMM columns at nb writes NJ * 8 output columns at nb / 2.
+// Same structure rules as above: the vectors are hoisted and retired with drain_visible_loads (the only compiler-visible loads; rows of ln_rt
+// are clamped, so every load is consumed on every path), stores are hand-written at immediate offsets from one base address per row.
+VR_DEV float silu_mul(float g, float u) {       // g * sigmoid(g) * u; log2(e) folded into the exponent
+    return g * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g)) * u;
+}
+
+template <int NI, int NJ, bool EDGE, bool HAS_LN, bool AL, typename ACC>
+VR_DEV void gemm_epilogue_gated_impl(const GemmArgs& p, const ACC (&acc)[NI][NJ], int mb, int nb, int fr, int hg) {
+    static_assert(AccGeom<ACC>::QN == 1 && (NJ % 2) == 0, "gated epilogue: 16x16 accumulators, an even number of column blocks");
+    constexpr int NP = NJ / 2;                               // output blocks of 16 columns per wave tile
+    constexpr bool WIDE = AL && (NP % 2) == 0;
+    constexpr int CSTEP = WIDE ? 2 : 1;
+    float4 bg[NP], bu[NP], sg[HAS_LN ? NP : 1], su[HAS_LN ? NP : 1];
+#pragma unroll
+    for (int t = 0; t < NP; ++t) { bg[t] = float4{0.f, 0.f, 0.f, 0.f}; bu[t] = float4{0.f, 0.f, 0.f, 0.f}; }
+    const int gcol = nb + hg * 4;                            // this lane's first GEMM column (gate of output block 0)
+    if (p.bias) {
+#pragma unroll
+        for (int t = 0; t < NP; ++t) {
+            bg[t] = *reinterpret_cast<const float4*>(p.bias + gcol + 32 * t);
+            bu[t] = *reinterpret_cast<const float4*>(p.bias + gcol + 32 * t + 16);
+        }
+    }
+    float2 rt_all[HAS_LN ? NI : 1];
+    if (HAS_LN) {
+#pragma unroll
+        for (int t = 0; t < NP; ++t) {
+            sg[HAS_LN ? t : 0] = *reinterpret_cast<const float4*>(p.ln_s + gcol + 32 * t);
+            su[HAS_LN ? t : 0] = *reinterpret_cast<const float4*>(p.ln_s + gcol + 32 * t + 16);
+        }
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int m = mb + i * 16 + fr;
+            rt_all[i] = p.ln_rt[(EDGE && m >= p.M) ? p.M - 1 : m];
+        }
+    }
+    drain_visible_loads();
+    // WIDE: this lane's 8-column chunk of the block pair (t0, t0 + 1) starts at ocol + 16 t0 (even lanes: block t0, odd lanes: block t0 + 1)
+    const int ocol = (nb >> 1) + hg * 4 + ((WIDE && (hg & 1)) ? 12 : 0);
+    static_for<NI>([&](auto I) __attribute__((always_inline)) {
+        constexpr int i = decltype(I)::value;
+        const int m = mb + i * 16 + fr;
+        const bool ok = EDGE ? (m < p.M) : true;
+        char* crow = reinterpret_cast<char*>(p.C) + ((size_t)(ok ? m : p.M - 1) * p.ldc + ocol) * 2;
+        static_for<NP / CSTEP>([&](auto T0) __attribute__((always_inline)) {
+            constexpr int t0 = decltype(T0)::value * CSTEP;
+            u32x2 o2[CSTEP];
+            static_for<CSTEP>([&](auto TT) __attribute__((always_inline)) {
+                constexpr int tt = decltype(TT)::value, t = t0 + tt;
+                const f32x4 ag = acc[i][2 * t], au = acc[i][2 * t + 1];
+                float g0, g1, g2, g3, u0, u1, u2, u3;
+                if (HAS_LN) {       // rstd * (acc - mean * s) + bias'
+                    const float2 rt = rt_all[HAS_LN ? i : 0];
+                    const float4 s_g = sg[HAS_LN ? t : 0], s_u = su[HAS_LN ? t : 0];
+                    g0 = __builtin_fmaf(ag[0], rt.x, __builtin_fmaf(rt.y, s_g.x, bg[t].x)); g1 = __builtin_fmaf(ag[1], rt.x, __builtin_fmaf(rt.y, s_g.y, bg[t].y));
+                    g2 = __builtin_fmaf(ag[2], rt.x, __builtin_fmaf(rt.y, s_g.z, bg[t].z)); g3 = __builtin_fmaf(ag[3], rt.x, __builtin_fmaf(rt.y, s_g.w, bg[t].w));
+                    u0 = __builtin_fmaf(au[0], rt.x, __builtin_fmaf(rt.y, s_u.x, bu[t].x)); u1 = __builtin_fmaf(au[1], rt.x, __builtin_fmaf(rt.y, s_u.y, bu[t].y));
+                    u2 = __builtin_fmaf(au[2], rt.x, __builtin_fmaf(rt.y, s_u.z, bu[t].z)); u3 = __builtin_fmaf(au[3], rt.x, __builtin_fmaf(rt.y, s_u.w, bu[t].w));
+                } else {
+                    g0 = ag[0] + bg[t].x; g1 = ag[1] + bg[t].y; g2 = ag[2] + bg[t].z; g3 = ag[3] + bg[t].w;
+                    u0 = au[0] + bu[t].x; u1 = au[1] + bu[t].y; u2 = au[2] + bu[t].z; u3 = au[3] + bu[t].w;
+                }
+                o2[tt] = u32x2{pack_bf16(silu_mul(g0, u0), silu_mul(g1, u1)), pack_bf16(silu_mul(g2, u2), silu_mul(g3, u3))};
+                if (!WIDE && ok) store_b64_at<t * 32>(crow, o2[tt]);
+            });
+            if (WIDE) {             // as the row-major epilogue: even lanes (own t0, partner's t0), odd lanes (partner's t0 + 1, own t0 + 1)
+                const auto w0 = __builtin_amdgcn_permlane16_swap(o2[0][0], o2[CSTEP - 1][0], false, false);
+                const auto w1 = __builtin_amdgcn_permlane16_swap(o2[0][1], o2[CSTEP - 1][1], false, false);
+                if (ok) {
+                    const u32x4 q4 = {(unsigned)w0[0], (unsigned)w1[0], (unsigned)w0[1], (unsigned)w1[1]};
+                    store_b128_at<t0 * 32>(crow, __builtin_bit_cast(f32x4, q4));
+                }
+            }
+        });
+    });
+}
+
+template <int NI, int NJ, typename ACC>
+VR_DEV void gemm_epilogue_gated(const GemmArgs& p, const ACC (&acc)[NI][NJ], int mb, int nb, int fr, int hg) {
+    const bool interior = mb + NI * 16 <= p.M;               // uniform decisions, one compiled body per value
+    const bool al = (p.ldc & 7) == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0;
+    if (p.ln_rt) {
+        if (al) {
+            if (interior) gemm_epilogue_gated_impl<NI, NJ, false, true, true>(p, acc, mb, nb, fr, hg);
+            else gemm_epilogue_gated_impl<NI, NJ, true, true, true>(p, acc, mb, nb, fr, hg);
+        } else {
+            if (interior) gemm_epilogue_gated_impl<NI, NJ, false, true, false>(p, acc, mb, nb, fr, hg);
+            else gemm_epilogue_gated_impl<NI, NJ, true, true, false>(p, acc, mb, nb, fr, hg);
+        }
+    } else {
+        if (al) {
+            if (interior) gemm_epilogue_gated_impl<NI, NJ, false, false, true>(p, acc, mb, nb, fr, hg);
+            else gemm_epilogue_gated_impl<NI, NJ, true, false, true>(p, acc, mb, nb, fr, hg);
+        } else {
+            if (interior) gemm_epilogue_gated_impl<NI, NJ, false, false, false>(p, acc, mb, nb, fr, hg);
+            else gemm_epilogue_gated_impl<NI, NJ, true, false, false>(p, acc, mb, nb, fr, hg);
+        }
+    }
+}
+
 // V^T scatter: vt[n * ldc + perm16(m)], four consecutive tokens per 8-byte store (layout: see attention.hip)
 template <int NI, int NJ, bool HAS_LN, typename ACC>
 VR_DEV void gemm_epilogue_vt_impl(const GemmArgs& p, const ACC (&acc)[NI][NJ], int mb, int nb, int fr, int hg) {

@@ -147,7 +147,9 @@ extern "C" int visrep_vit_forward_cpu(const visrep_vit_config* c, const visrep_v
     std::vector<float>().swap(cols);
     std::vector<float>().swap(emb);
     if (c->pre_ln) layernorm_rows_cpu(hidden, w->pre_ln_g, w->pre_ln_b, hidden, M, d, c->eps, threads);
-    std::vector<float> h((size_t)M * d), qkv((size_t)M * 3 * d), att((size_t)M * d), mid((size_t)M * mlp), tmp((size_t)M * d);
+    const bool swiglu = c->act == VISREP_ACT_SWIGLU;          // HF Dinov2SwiGLUFFN: w1 [2 mlp, d] = gate rows, then value rows
+    const int mw = swiglu ? 2 * mlp : mlp;                    // width of fc1's output
+    std::vector<float> h((size_t)M * d), qkv((size_t)M * 3 * d), att((size_t)M * d), mid((size_t)M * mw), tmp((size_t)M * d);
     const float scale = 1.0f / sqrtf((float)dh);
     for (int l = 0; l < n_layers; ++l) {
         const visrep_vit_layer& L = w->layers[l];
@@ -184,12 +186,19 @@ extern "C" int visrep_vit_forward_cpu(const visrep_vit_config* c, const visrep_v
                 for (int i = 0; i < d; ++i) hidden[(size_t)r * d + i] += (L.ls1 ? L.ls1[i] : 1.f) * tmp[(size_t)r * d + i];
         });
         layernorm_rows_cpu(hidden, L.ln2_g, L.ln2_b, h.data(), M, d, c->eps, threads);
-        linear_rows(h.data(), d, (const float*)L.w1, d, L.b1, mid.data(), mlp, M, mlp, d, threads);
+        linear_rows(h.data(), d, (const float*)L.w1, d, L.b1, mid.data(), mw, M, mw, d, threads);
         const int act = c->act;
-        parallel_for((M + 15) / 16, threads, [&](long blk) {
-            for (size_t i = (size_t)blk * 16 * mlp; i < (size_t)std::min<long>(M, blk * 16 + 16) * mlp; ++i) mid[i] = act_cpu(mid[i], act);
-        });
-        linear_rows(mid.data(), mlp, (const float*)L.w2, mlp, L.b2, tmp.data(), d, M, d, mlp, threads);
+        if (swiglu) {                                         // x1, x2 = chunk(2); silu(x1) * x2, left in the first mlp columns of each row
+            parallel_for(M, threads, [&](long r) {
+                float* row = mid.data() + (size_t)r * mw;
+                for (int i = 0; i < mlp; ++i) row[i] = row[i] / (1.0f + expf(-row[i])) * row[mlp + i];
+            });
+        } else {
+            parallel_for((M + 15) / 16, threads, [&](long blk) {
+                for (size_t i = (size_t)blk * 16 * mlp; i < (size_t)std::min<long>(M, blk * 16 + 16) * mlp; ++i) mid[i] = act_cpu(mid[i], act);
+            });
+        }
+        linear_rows(mid.data(), mw, (const float*)L.w2, mlp, L.b2, tmp.data(), d, M, d, mlp, threads);
         parallel_for((M + 63) / 64, threads, [&](long blk) {
             for (long r = blk * 64; r < std::min<long>(M, blk * 64 + 64); ++r)
                 for (int i = 0; i < d; ++i) hidden[(size_t)r * d + i] += (L.ls2 ? L.ls2[i] : 1.f) * tmp[(size_t)r * d + i];

@@ -172,6 +172,42 @@ extern "C" int visrep_gemm_bf16_ln(const void* A, int lda, const void* W, int ld
     return visrep_gemm_dispatch(a, (hipStream_t)stream);
 }
 
+extern "C" int visrep_gemm_bf16_gated(const void* A, int lda, const void* W, int ldw, const float* bias, const void* ln_rt, const float* ln_s,
+                                      void* C, int ldc, int M, int N, int K, void* stream) {
+    if (!A || !W || !C || ((ln_rt == nullptr) != (ln_s == nullptr))) return visrep_set_error(VISREP_ERR_ARG, "gemm_gated: null pointer (ln_rt and ln_s come together)");
+    if ((uintptr_t)C & 7) return visrep_set_error(VISREP_ERR_ARG, "gemm_gated: C must be 8-byte aligned");
+    GemmArgs a{};
+    a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = (bf16_t*)C; a.bias = bias; a.ln_rt = (const float2*)ln_rt; a.ln_s = ln_s;
+    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.epi = EPI_GATED;
+    return visrep_gemm_dispatch(a, (hipStream_t)stream);
+}
+
+thread_local int t_visrep_fuse_gate = 1;
+extern "C" int visrep_set_fuse_gate(int on) {
+    const int old = t_visrep_fuse_gate;
+    t_visrep_fuse_gate = on ? 1 : 0;
+    return old;
+}
+
+extern "C" int visrep_debug_gated_refusal(int which) {
+    static char dummy[64];                                       // never dereferenced: every combination below is refused before a launch
+    GemmArgs a{};
+    a.A = (const bf16_t*)dummy; a.W = (const bf16_t*)dummy; a.C = (bf16_t*)dummy;
+    a.M = 256; a.N = 256; a.K = 64; a.lda = 64; a.ldw = 64; a.ldc = 128; a.epi = EPI_GATED;
+    switch (which) {
+        case 1: a.conv = 1; a.cH = a.cW = a.cHo = a.cWo = 16; a.cC = 64; a.cstride = 1; a.cpad = 1; a.K = 576; break;
+        case 2: a.a_period = 4; a.a_stride = 8; a.a_first = 0; break;
+        case 3: a.stat_rt = (float2*)dummy; a.stat_partial = (float2*)dummy; break;
+        case 4: a.gn_partial = (float2*)dummy; a.gn_cpg = 4; a.gn_hw = 128; break;
+        default: return visrep_set_error(VISREP_ERR_ARG, "debug_gated_refusal: which must be 1 .. 4");
+    }
+    const long before = t_visrep_routes[VISREP_ROUTE_GEMM_256] + t_visrep_routes[VISREP_ROUTE_GEMM_128] + t_visrep_routes[VISREP_ROUTE_SPLITK];
+    const int rc = visrep_gemm_dispatch(a, nullptr);
+    const long after = t_visrep_routes[VISREP_ROUTE_GEMM_256] + t_visrep_routes[VISREP_ROUTE_GEMM_128] + t_visrep_routes[VISREP_ROUTE_SPLITK];
+    if (rc == 0 || after != before) { visrep_set_error(VISREP_ERR_ARG, "debug_gated_refusal: the dispatcher accepted the combination"); return 1; }
+    return rc;
+}
+
 extern "C" int visrep_gemm_bf16_rows(const void* A, int lda, int row_period, int row_stride, int row_first, const void* W, int ldw,
                                      const float* bias, const void* ln_rt, const float* ln_s, void* C, int ldc, int M, int N, int K, int epilogue,
                                      int act, void* stream) {
@@ -285,7 +321,9 @@ Ws layout(const visrep_vit_config* c, int B) {
     w.qk = off;  off += up(Mp * 2 * da * 2, 256);
     w.vt = off;  off += up(da * w.ldvt * 2, 256);
     w.vcls = off; off += up((size_t)B * da * 2, 256);               // V rows of the CLS tokens (image-aligned attention)
-    const size_t mlp_b = Mp * c->mlp * 2;
+    // SwiGLU towers: the gated fc1 writes [Mp, mlp] like every other activation; the unfused A/B route (visrep_set_fuse_gate(0)) keeps the
+    // [Mp, 2 mlp] GEMM output in front of it
+    const size_t mlp_b = Mp * c->mlp * 2 * ((c->act == VISREP_ACT_SWIGLU && !t_visrep_fuse_gate) ? 3 : 1);
     const size_t cols_b = up((size_t)B * (c->tokens - c->has_cls), 128) * c->kpad * 2;
     w.mlp = off; off += up(mlp_b > cols_b ? mlp_b : cols_b, 256);   // im2col columns alias the MLP buffer
     w.rt = off;  off += up((Mp + 8) * sizeof(float2), 256);         // folded-LayerNorm row statistics (zero past M)
@@ -317,6 +355,7 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
         return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: d, mlp % 128 and kpad % 64 required (mlp = the zero-padded MLP width)");
     const int grid = c->image_size / c->patch;
     if (grid * grid + (c->has_cls ? 1 : 0) != c->tokens) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: tokens != grid^2 + cls");
+    if (c->act < VISREP_ACT_NONE || c->act > VISREP_ACT_SWIGLU) return visrep_set_error(VISREP_ERR_ARG, "vit_forward: unknown activation code");
     hipStream_t s = (hipStream_t)stream;
     const Ws L = layout(c, B);
     char* base = (char*)workspace;
@@ -395,6 +434,18 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
         }
         f.lda = d; f.K = d; f.M = M; f.W = (const bf16_t*)W.w1; f.ldw = d; f.N = c->mlp; f.C = mlp; f.ldc = c->mlp;
         f.bias = W.b1; f.epi = EPI_ACT; f.act = c->act;
+        if (c->act == VISREP_ACT_SWIGLU) {                   // HF Dinov2SwiGLUFFN: w1 has 2 mlp rows
+            f.N = 2 * c->mlp; f.act = 0;
+            if (t_visrep_fuse_gate) {                            // gate in the epilogue: the [M, 2 mlp] intermediate never exists (w1 interleaved)
+                f.epi = EPI_GATED;
+                VR_TRY(visrep_gemm_dispatch(f, s));
+            } else {                                             // A/B baseline: plain GEMM behind the hidden buffer, then the element-wise pass (w1 in HF order)
+                bf16_t* gu = mlp + up(M, 128) * (size_t)c->mlp;
+                f.epi = EPI_BIAS; f.C = gu; f.ldc = 2 * c->mlp;
+                VR_TRY(visrep_gemm_dispatch(f, s));
+                VR_TRY(visrep_swiglu(gu, 2 * c->mlp, mlp, c->mlp, M, c->mlp, stream));
+            }
+        } else
         VR_TRY(visrep_gemm_dispatch(f, s));
         f.ln_rt = nullptr; f.ln_s = nullptr;
         f.A = mlp; f.lda = c->mlp; f.K = c->mlp; f.W = (const bf16_t*)W.w2; f.ldw = c->mlp; f.N = d; f.C = x; f.ldc = d;

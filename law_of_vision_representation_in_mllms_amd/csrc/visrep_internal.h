@@ -9,7 +9,8 @@
 
 typedef unsigned short bf16_t;
 
-enum { EPI_BIAS = 0, EPI_ACT = 1, EPI_RESID = 2, EPI_VT = 3, EPI_PATCH = 4, EPI_F32 = 5, EPI_F32X = 6 };
+enum { EPI_BIAS = 0, EPI_ACT = 1, EPI_RESID = 2, EPI_VT = 3, EPI_PATCH = 4, EPI_F32 = 5, EPI_F32X = 6, EPI_GATED = 7 };
+static_assert(EPI_GATED == VISREP_EPI_GATED, "the gated epilogue's code is public");
 
 struct GemmArgs {
     const bf16_t* A;      // [M, K] row-major, leading dimension lda (elements)
@@ -111,6 +112,7 @@ extern thread_local int t_visrep_gemm_variant;   // 1 = 128x128 kernel, 2 / 5 = 
 int visrep_attention_ab_launch(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* out, int ldo,
                                int B, int Tq, int Tk, int H, int kv_shared, int causal, float scale, hipStream_t st);
 extern thread_local int t_visrep_attn_variant;
+extern thread_local int t_visrep_fuse_gate;     // A/B knob (visrep_set_fuse_gate): 1 = SwiGLU towers run fc1 with the gated epilogue, 0 = EPI_BIAS + visrep_swiglu
 int visrep_set_error(int code, const char* msg);
 // Which kernel family a call was routed to - per-THREAD launch counters read by visrep_debug_routes() (tests assert that a shape takes the
 // route it was tuned for; two integer adds per launch, no device work).  Indices are VISREP_ROUTE_* of include/visrep.h.

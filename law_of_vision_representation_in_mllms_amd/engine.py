@@ -46,16 +46,26 @@ def pad_tower_weights(spec: ViTSpec, layer: dict, dp: int, mp: int) -> dict:
         wo[:, :, :dh] = L["wo"].detach().float().reshape(d, H, dh)
         L["wo"] = wo.reshape(d, H * dp)
     if mp != m:
-        w1 = torch.zeros(mp, d)
-        w1[:m] = L["w1"].detach().float()
+        halves = 2 if spec.act == "swiglu" else 1          # swiglu: the gate half and the value half are padded each (silu(0) * 0 = 0)
+        w1 = torch.zeros(halves, mp, d)
+        w1[:, :m] = L["w1"].detach().float().reshape(halves, m, d)
         w2 = torch.zeros(d, mp)
         w2[:, :m] = L["w2"].detach().float()
-        L["w1"], L["w2"] = w1, w2
+        L["w1"], L["w2"] = w1.reshape(halves * mp, d), w2
         if L.get("b1") is not None:
-            b1 = torch.zeros(mp)
-            b1[:m] = L["b1"].detach().float()
-            L["b1"] = b1
+            b1 = torch.zeros(halves, mp)
+            b1[:, :m] = L["b1"].detach().float().reshape(halves, m)
+            L["b1"] = b1.reshape(halves * mp)
     return L
+
+
+def swiglu_interleave_index(mp: int) -> torch.Tensor:
+    """Row order of the gated GEMM (visrep_gemm_bf16_gated) in terms of HF chunk order [gate 0 .. mp | value 0 .. mp]: GEMM row 32 t + r is the
+    gate row of hidden unit 16 t + r, row 32 t + 16 + r its value row (r < 16).  `x[idx]` interleaves, `out[idx] = y` undoes it."""
+    if mp % 16:
+        raise ValueError("swiglu interleave: the (padded) hidden width must be a multiple of 16")
+    unit = torch.arange(mp).reshape(mp // 16, 1, 16)
+    return torch.cat([unit, unit + mp], dim=1).reshape(2 * mp)
 
 
 _SCRATCH = {}
@@ -84,7 +94,7 @@ class VitEngine:
     """
 
     def __init__(self, spec: ViTSpec, weights: dict, device: Optional[torch.device] = None, fuse_ln: Optional[bool] = None,
-                 head_pad: Optional[int] = None):
+                 head_pad: Optional[int] = None, fuse_gate: Optional[bool] = None):
         """head_pad: lanes per head in the device buffers, None = head_pad_for(d / heads) (64 -> 64, 65 .. 96 -> 96, 97 .. 128 -> 128);
         128 for a head of 65 .. 96 is the route attn_fwd96 replaced (attn_fwd<2> on heads padded to 128), kept reachable for A/B runs.
         The MLP width is padded to a multiple of 128 alike (pad_tower_weights).
@@ -98,6 +108,9 @@ class VitEngine:
         self.lib = _lib.require_gpu()
         import os
         self.fuse_ln = (os.environ.get("VISREP_FUSE_LN", "1") != "0") if fuse_ln is None else bool(fuse_ln)
+        # SwiGLU towers (DINOv2-giant): fc1 with the gate in the GEMM epilogue (default; w1 / b1 / s1 in the 16-row interleave) or, with
+        # fuse_gate=False / VISREP_FUSE_GATE=0, as a plain GEMM + the element-wise visrep_swiglu pass (A/B baseline, profiles/swiglu.md)
+        self.fuse_gate = (os.environ.get("VISREP_FUSE_GATE", "1") != "0") if fuse_gate is None else bool(fuse_gate)
         self.spec = spec
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         if spec.d % spec.heads:
@@ -166,6 +179,13 @@ class VitEngine:
                 L["wqkv"] = L["wqkv"].detach().float().to(torch.bfloat16).float() * qc[:, None]
                 if L.get("bqkv") is not None:
                     L["bqkv"] = L["bqkv"].detach().float() * qc
+            if spec.act == "swiglu" and self.fuse_gate:                        # after the fold (per row): w1, b1 and s1 move together
+                idx = swiglu_interleave_index(self.mlp_pad)
+                L["w1"] = L["w1"][idx]
+                if L.get("b1") is not None:
+                    L["b1"] = L["b1"][idx]
+                if extra["s1"] is not None:
+                    extra["s1"] = extra["s1"][idx]
             for k in ("wqkv", "wo", "w1", "w2"):
                 setattr(ent, k, mat(L[k]).data_ptr())
             for k in ("ln1_g", "ln1_b", "bqkv", "bo", "ls1", "ln2_g", "ln2_b", "b1", "b2", "ls2"):
@@ -188,7 +208,9 @@ class VitEngine:
     def workspace(self, B: int) -> torch.Tensor:
         ws = self._ws.get(B)
         if ws is None:
+            old_knob = self.lib.visrep_set_fuse_gate(int(self.fuse_gate))          # the unfused SwiGLU route keeps a wider MLP buffer
             nbytes = self.lib.visrep_vit_workspace_bytes(C.byref(self._cfg), B)
+            self.lib.visrep_set_fuse_gate(old_knob)
             # a few batch sizes stay resident; a workspace that a HIP graph captured (the image-variation featurizer records this engine's
             # forward inside its own graph) is PINNED: a replayed graph keeps using the pointer it saw, so it is never evicted
             for old in [b for b in self._ws if b not in self._pinned][: max(0, len(self._ws) - len(self._pinned) - 5)]:
@@ -216,9 +238,11 @@ class VitEngine:
             out = torch.empty(B, s.tokens, s.d, dtype=torch.bfloat16, device=self.device)
         ws = self.workspace(B)
         with torch.cuda.device(self.device):
+            old_knob = self.lib.visrep_set_fuse_gate(int(self.fuse_gate))          # per-thread, host side: which fc1 route this engine's weights are packed for
             rc = self.lib.visrep_vit_forward(C.byref(self._cfg), C.byref(self._w), _lib.ptr(px),
                                              _lib.F32 if px.dtype == torch.float32 else _lib.BF16,
                                              _lib.ptr(out), B, n_layers, _lib.ptr(ws), _lib.stream_ptr())
+            self.lib.visrep_set_fuse_gate(old_knob)
         _lib.check(rc, "visrep_vit_forward")
         return out
 
@@ -549,6 +573,32 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
     rc = lib.visrep_gemm_bf16(_lib.ptr(a), a.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(bias), _lib.ptr(out), out.stride(0),
                               M, N, K, epilogue, _lib.ACT[act], _lib.ptr(resid), _lib.ptr(ls), _lib.stream_ptr())
     _lib.check(rc, "visrep_gemm_bf16")
+    return out
+
+
+def gemm_gated(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, ln_rt: Optional[torch.Tensor] = None,
+               ln_s: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """SwiGLU GEMM (visrep_gemm_bf16_gated): a [M, K] bf16, w [2 mp, K] bf16 with gate / value rows interleaved in blocks of 16
+    (swiglu_interleave_index), bias / ln_s [2 mp] in the same order -> [M, mp] bf16 = silu(gate) * value.  `out` may be a column window."""
+    lib = _lib.require_gpu()
+    M, K = a.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty(M, N // 2, dtype=torch.bfloat16, device=a.device)
+    rc = lib.visrep_gemm_bf16_gated(_lib.ptr(a), a.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(bias), _lib.ptr(ln_rt), _lib.ptr(ln_s),
+                                    _lib.ptr(out), out.stride(0), M, N, K, _lib.stream_ptr())
+    _lib.check(rc, "visrep_gemm_bf16_gated")
+    return out
+
+
+def swiglu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """silu(x[:, :F]) * x[:, F:] (HF chunk order) for bf16 or fp32 x [M, 2 F] (visrep_swiglu / visrep_swiglu_f32)."""
+    lib = _lib.require_gpu()
+    M, F = x.shape[0], x.shape[1] // 2
+    if out is None:
+        out = torch.empty(M, F, dtype=x.dtype, device=x.device)
+    fn = lib.visrep_swiglu_f32 if x.dtype == torch.float32 else lib.visrep_swiglu
+    _lib.check(fn(_lib.ptr(x), x.stride(0), _lib.ptr(out), out.stride(0), M, F, _lib.stream_ptr()), "visrep_swiglu")
     return out
 
 

@@ -11,6 +11,8 @@ Packed layout (fp32 torch tensors on CPU):
   pre_ln_g / pre_ln_b [d]|None
   layers[i]: ln1_g ln1_b wqkv[3d,d] bqkv[3d] wo[d,d] bo[d] ls1[d]|None
              ln2_g ln2_b w1[m,d] b1[m] w2[d,m] b2[d] ls2[d]|None
+  act "swiglu" (HF Dinov2SwiGLUFFN): m = spec.mlp is the hidden width h, w1 [2h, d] / b1 [2h] are weights_in in HF order
+  (the h gate rows x1, then the h value rows x2), w2 [d, h] is weights_out.
 """
 from __future__ import annotations
 
@@ -30,7 +32,7 @@ class ViTSpec:
     layers: int
     heads: int
     mlp: int
-    act: str            # quick_gelu | gelu | gelu_tanh
+    act: str            # quick_gelu | gelu | gelu_tanh | swiglu (gated MLP: `mlp` is the hidden width, fc1 has 2 * mlp rows)
     eps: float
     has_cls: bool
     pre_ln: bool        # CLIP pre_layrnorm
@@ -38,6 +40,10 @@ class ViTSpec:
     layerscale: bool    # DINOv2
     family: str         # clip | dinov2 | siglip
     pos_grid: int = 0   # native position-embedding grid (DINOv2: 37); 0 = image_size // patch
+
+    @property
+    def fc1_rows(self) -> int:
+        return 2 * self.mlp if self.act == "swiglu" else self.mlp
 
     @property
     def grid(self) -> int:
@@ -74,7 +80,16 @@ SPECS: Dict[str, ViTSpec] = {
                                                 "gelu_tanh", 1e-6, False, False, True, False, "siglip"),
     "laion/CLIP-ViT-H-14-laion2B-s32B-b79K": ViTSpec("laion/CLIP-ViT-H-14-laion2B-s32B-b79K", 224, 14, 1280, 32, 16,
                                                      5120, "gelu", 1e-5, True, True, False, False, "clip"),
+    # SwiGLU FFN (HF Dinov2SwiGLUFFN, use_swiglu_ffn): hidden width (int(int(1536 * 4) * 2 / 3) + 7) // 8 * 8 = 4096, fc1 [8192, 1536].  Not in
+    # the reference registry either; as recalled from the public config, a local `config.json` wins.
+    "facebook/dinov2-giant": ViTSpec("facebook/dinov2-giant", 224, 14, 1536, 40, 24, 4096,
+                                     "swiglu", 1e-6, True, False, True, True, "dinov2", pos_grid=37),
 }
+
+
+def swiglu_hidden(d: int, mlp_ratio: float) -> int:
+    """Hidden width of HF Dinov2SwiGLUFFN: two thirds of d * mlp_ratio, rounded up to a multiple of 8 (modeling_dinov2.py)."""
+    return (int(int(d * mlp_ratio) * 2 / 3) + 7) // 8 * 8
 
 
 def tiny_spec(family: str, act: Optional[str] = None, image_size: int = 28, patch: int = 7, d: int = 64,
@@ -105,8 +120,10 @@ def spec_from_hf_config(cfg, name: str = "", crop_size: Optional[int] = None) ->
                        cfg.num_attention_heads, cfg.intermediate_size, act, cfg.layer_norm_eps,
                        True, True, False, False, "clip")
     if mt.startswith("dinov2"):
+        swiglu = bool(getattr(cfg, "use_swiglu_ffn", False))     # giant: gated MLP, hidden_act is not used by it
+        mlp = swiglu_hidden(cfg.hidden_size, cfg.mlp_ratio) if swiglu else int(cfg.hidden_size * cfg.mlp_ratio)
         return ViTSpec(name, int(crop_size or 224), cfg.patch_size, cfg.hidden_size, cfg.num_hidden_layers,
-                       cfg.num_attention_heads, int(cfg.hidden_size * cfg.mlp_ratio), act, cfg.layer_norm_eps,
+                       cfg.num_attention_heads, mlp, "swiglu" if swiglu else act, cfg.layer_norm_eps,
                        True, False, True, True, "dinov2", pos_grid=cfg.image_size // cfg.patch_size)
     if mt.startswith("siglip"):
         return ViTSpec(name, cfg.image_size, cfg.patch_size, cfg.hidden_size, cfg.num_hidden_layers,
@@ -181,6 +198,8 @@ def pack_hf_state_dict(sd: Dict[str, torch.Tensor], spec: ViTSpec) -> dict:
                      o="attention.output.dense", ln1="norm1", ln2="norm2", fc1="mlp.fc1", fc2="mlp.fc2")
     else:
         raise ValueError(spec.family)
+    if spec.act == "swiglu":                                     # HF Dinov2SwiGLUFFN: weights_in [2h, d] (chunk order), weights_out [d, h]
+        names.update(fc1="mlp.weights_in", fc2="mlp.weights_out")
     # The checkpoint's own grid stays in the packed weights: a later change of resolution (weights_at_resolution) must resize from
     # IT, once, like HF's interpolate_pos_encoding does (37 x 37 -> target), not from the already-resized table (37 -> 16 -> 24).
     w["pos_native"] = w["pos"]
@@ -213,6 +232,7 @@ def synthetic_weights(spec: ViTSpec, seed: int = 1, n_layers: Optional[int] = No
     """
     rs = np.random.RandomState(seed)
     d, m, p = spec.d, spec.mlp, spec.patch
+    m1 = spec.fc1_rows                                           # swiglu: gate rows, then value rows (other activations: m, the same draws as ever)
     import os
     mode = os.environ.get("VISREP_FAST_SYNTHETIC")                     # throughput runs only: torch generator ("1") / drawn in HBM ("cuda")
     fdev = "cuda" if mode == "cuda" and torch.cuda.is_available() else "cpu"
@@ -237,7 +257,7 @@ def synthetic_weights(spec: ViTSpec, seed: int = 1, n_layers: Optional[int] = No
             "wo": rn(d, d), "bo": rn(d),
             "ls1": rn(d, std=0.02, mean=0.1) if spec.layerscale else None,
             "ln2_g": rn(d, std=0.1, mean=1.0), "ln2_b": rn(d),
-            "w1": rn(m, d), "b1": rn(m), "w2": rn(d, m), "b2": rn(d),
+            "w1": rn(m1, d), "b1": rn(m1), "w2": rn(d, m), "b2": rn(d),
             "ls2": rn(d, std=0.02, mean=0.1) if spec.layerscale else None,
         })
     w["layers"] = layers

@@ -8,7 +8,11 @@
   3. the attention kernels (attn_fwd*, attention.hip) use no scratch at all: their Q fragments and O accumulators are sized to the register
      file (attn_fwd96: 136 VGPRs, no AGPRs), and one spilled accumulator costs a scratch round trip per key tile.
 
-usage: python tools/isa_check.py [file.hip ...]      (default: the product library's persistent kernels)"""
+  4. the gated (SwiGLU, EPI_GATED = 7) instantiations of both persistent GEMMs exist and obey 1 and 2 with NO scratch at all: their epilogue adds
+     no row loads, so a spill there would be a regression of the epilogue itself.
+
+usage: python tools/isa_check.py [--sizes] [file.hip ...]      (default: the product library's persistent kernels)
+--sizes also prints every kernel's code length (to compare the existing instantiations with a parent build)."""
 import os
 import re
 import subprocess
@@ -17,8 +21,11 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "law_of_vision_representation_in_mllms_amd", "csrc")
-FILES = sys.argv[1:] or ["gemm_bf16_v5.hip", "gemm_bf16_v2.hip", "ascore.hip", "attention.hip"]
-NO_SCRATCH = ("attn_fwd",)                  # kernels (by name fragment) that must not touch scratch
+SIZES = "--sizes" in sys.argv[1:]
+FILES = [a for a in sys.argv[1:] if a != "--sizes"] or ["gemm_bf16_v5.hip", "gemm_bf16_v2.hip", "ascore.hip", "attention.hip"]
+# kernels (by name fragment) that must not touch scratch; Li7E = template argument EPI_GATED of gemm_bf16_256q / gemm_bf16_256
+NO_SCRATCH = ("attn_fwd", "gemm_bf16_256qILi7E", "gemm_bf16_256ILi7E")
+REQUIRED = {"gemm_bf16_v5.hip": ("gemm_bf16_256qILi7ELb1E", "gemm_bf16_256qILi7ELb0E"), "gemm_bf16_v2.hip": ("gemm_bf16_256ILi7E",)}
 bad = 0
 for f in FILES:
     with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
@@ -29,7 +36,7 @@ for f in FILES:
             sys.exit(r.stderr[-2000:])
         lines = open(tmp.name).read().splitlines()
     kernel, wait_at = None, None
-    hits, scratch = {}, {}
+    hits, scratch, size = {}, {}, {}
     for i, ln in enumerate(lines):
         m = re.match(r"^(_Z\w+):", ln)
         if m:
@@ -44,6 +51,16 @@ for f in FILES:
         m = re.search(r"\.private_segment_fixed_size:\s*(\d+)", ln) or re.search(r"; ScratchSize: (\d+)", ln)
         if m and kernel:
             scratch[kernel] = max(scratch.get(kernel, 0), int(m.group(1)))
+        m = re.search(r"; codeLenInByte = (\d+)", ln)
+        if m and kernel:
+            size[kernel] = int(m.group(1))
+    for frag in REQUIRED.get(os.path.basename(f), ()):
+        if not any(frag in k for k in scratch):
+            print(f"{f}: no kernel matching {frag} (the gated instantiation is missing)")
+            bad += 1
+    if SIZES:
+        for k in sorted(size):
+            print(f"{f}: {k}: {size[k]} bytes of code, {scratch.get(k, 0)} bytes of scratch")
     for k, n in hits.items():
         print(f"{f}: {k}: {n} K-loop header(s) behind s_waitcnt vmcnt(0)")
         bad += 1
