@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define VISREP_VERSION 630   /* 630: SwiGLU-FFN towers (DINOv2-giant) - VISREP_ACT_SWIGLU = 4 in visrep_vit_config::act (w1 / b1 / s1 then have 2 * mlp rows), VISREP_EPI_GATED, visrep_gemm_bf16_gated, visrep_swiglu, visrep_swiglu_f32, visrep_set_fuse_gate, visrep_debug_gated_refusal (new exports / newly accepted argument values; no struct layout change).  620: head widths other than 64 in the bf16 tower - visrep_vit_config grows head_dim / head_pad (struct change), visrep_mhsa_fwd takes head_dim 64 | 96 | 128, visrep_attention_fwd head_dim 96, route id 12; visrep_im2col and visrep_vit_forward_cpu no longer refuse an image side that is not a multiple of the patch - they floor the division as Conv2d does (newly accepted argument values).  610: visrep_cscore_transfer_packed2 / visrep_cscore_transfer2_cpu, the key-point transfer on two per-encoder banks (new exports only).  600 = round 6: reserved CUs, GEMM tile-walk knob, gemm variants 6-8, visrep_masked_nn_min_f32, window < 0 in the C-score transfers (new exports / newly accepted argument values only).  500 = round 5: device CU count, routing counters, MFMA probe, A-score reference arithmetic, host twins (new exports only).  410 = round 4: split-route `products`, stream-keyed scratch, per-thread knobs (changed signatures); 410: q_prescaled = 2, row-mapped GEMM, image-aligned / wide-head attention, conv + GroupNorm partials */
+#define VISREP_VERSION 640   /* 640: DINOv2-with-registers towers - visrep_vit_config grows a trailing `registers` (struct change), visrep_vit_weights::cls may be a [1 + registers, d] table, visrep_mhsa_prefix_fwd / visrep_mhsa_prefix_supported / visrep_prefix_rows, route id 13.  630: SwiGLU-FFN towers (DINOv2-giant) - VISREP_ACT_SWIGLU = 4 in visrep_vit_config::act (w1 / b1 / s1 then have 2 * mlp rows), VISREP_EPI_GATED, visrep_gemm_bf16_gated, visrep_swiglu, visrep_swiglu_f32, visrep_set_fuse_gate, visrep_debug_gated_refusal (new exports / newly accepted argument values; no struct layout change).  620: head widths other than 64 in the bf16 tower - visrep_vit_config grows head_dim / head_pad (struct change), visrep_mhsa_fwd takes head_dim 64 | 96 | 128, visrep_attention_fwd head_dim 96, route id 12; visrep_im2col and visrep_vit_forward_cpu no longer refuse an image side that is not a multiple of the patch - they floor the division as Conv2d does (newly accepted argument values).  610: visrep_cscore_transfer_packed2 / visrep_cscore_transfer2_cpu, the key-point transfer on two per-encoder banks (new exports only).  600 = round 6: reserved CUs, GEMM tile-walk knob, gemm variants 6-8, visrep_masked_nn_min_f32, window < 0 in the C-score transfers (new exports / newly accepted argument values only).  500 = round 5: device CU count, routing counters, MFMA probe, A-score reference arithmetic, host twins (new exports only).  410 = round 4: split-route `products`, stream-keyed scratch, per-thread knobs (changed signatures); 410: q_prescaled = 2, row-mapped GEMM, image-aligned / wide-head attention, conv + GroupNorm partials */
 
 enum { VISREP_BF16 = 0, VISREP_F32 = 1 };
 enum { VISREP_OK = 0, VISREP_ERR_ARG = -1, VISREP_ERR_SHAPE = -2, VISREP_ERR_LAUNCH = -3 };
@@ -90,7 +90,8 @@ enum {
     VISREP_ROUTE_CONV_HALO = 10,     /* conv3x3_halo: halo-resident 3x3 convolution with the input's GroupNorm + SiLU fused */
     VISREP_ROUTE_CONV_C8 = 11,       /* conv3x3_c8: the VAE's first convolution straight from 8-channel pixel tokens (no im2col) */
     VISREP_ROUTE_ATTN_96 = 12,       /* attn_fwd96 (head width 96: true widths 65 .. 96 zero-padded) */
-    VISREP_ROUTE_COUNT = 13
+    VISREP_ROUTE_ATTN_PREFIX = 13,   /* attn_fwd_prefix (image-aligned towers with CLS + register tokens) */
+    VISREP_ROUTE_COUNT = 14
 };
 int visrep_debug_routes(long* out, int reset);
 /* Matrix-pipe ceiling of THIS device under THIS process' conditions: `iters` bursts of 32 dependent-free v_mfma_f32_16x16x32_bf16 per wave,
@@ -223,6 +224,18 @@ int visrep_mhsa_cls_supported(int T);
 int visrep_mhsa_cls_fwd(const void* qk, int ldqk, const void* vt, int ldvt, const void* vcls, int ldvc, void* out, int ldo, int B, int T,
                         int H, int head_dim, void* stream);
 
+/* ---- image-aligned self-attention of a tower with a short PREFIX of NP non-patch tokens in front of 64 n patch tokens (DINOv2 with
+ * registers: CLS + 4 registers, T = 5 + 64 n: 261 at 224 px, 581 at 336 px), pre-scaled Q only.  It is visrep_mhsa_cls_fwd with NP side
+ * keys instead of one: qk as for visrep_mhsa_fwd; vt: V^T of the PATCH tokens only, [H*64, ldvt], column b (T - NP) + t - NP (perm16
+ * inside 16-token blocks), ldvt >= B (T - NP); vpre: the V rows of the prefix tokens [B NP, ldvp] row-major (row b NP + i), ldvp >= H*64.
+ * The prefix keys enter as the initial state of the online softmax: s_i = q.k_i, m = max_i s_i, p_i = 2^(s_i - m) kept in fp32, l = sum p_i,
+ * O = sum p_i v_i; then (T - NP) / 64 whole key tiles.  With NP = 1 the result equals visrep_mhsa_cls_fwd's bit for bit.
+ * visrep_mhsa_prefix_supported(T, NP): 1 <= NP <= 8, T - NP >= 64 and (T - NP) % 64 == 0.  qk and vt 16-byte aligned, vpre and out 8-byte
+ * aligned, none null; anything else is refused before any launch. */
+int visrep_mhsa_prefix_supported(int T, int NP);
+int visrep_mhsa_prefix_fwd(const void* qk, int ldqk, const void* vt, int ldvt, const void* vpre, int ldvp, void* out, int ldo, int B, int T,
+                           int NP, int H, int head_dim, void* stream);
+
 /* ---- general multi-head attention forward for the diffusion towers' transformer blocks (vendored diffusers
  * attention_processor.py AttnProcessor2_0 / SlicedAttnProcessor called from attention.py:241-283 BasicTransformerBlock):
  * self-attention (k/vt built from the same tokens, Tk = Tq) and cross-attention to the prompt (Tk = text length).
@@ -254,6 +267,9 @@ int visrep_attention_fwd(const void* q, int ldq, const void* k, int ldk, const v
  * 6 pixels unused).  Since 620; before, a side that was not a multiple of the patch was refused. */
 int visrep_im2col(const void* pixels, int pixel_dtype, void* cols, int B, int Himg, int Wimg, int patch, int Kpad, void* stream);
 int visrep_cls_rows(void* x, int ldx, const float* cls, const float* pos, int B, int T, int d, void* stream);
+/* the same for a prefix of `prefix` non-patch rows per image: x[b T + r] = table[r] + pos[r], r < prefix (table: [prefix, d], see
+ * visrep_vit_weights.cls).  prefix = 1 is visrep_cls_rows. */
+int visrep_prefix_rows(void* x, int ldx, const float* table, const float* pos, int B, int T, int prefix, int d, void* stream);
 int visrep_cast_f32_bf16(const float* src, void* dst, long n, void* stream);
 
 /* ---- composed tower forward: replaces `self.vision_tower(images, output_hidden_states=True).hidden_states[k]`
@@ -273,6 +289,10 @@ typedef struct {
      * rows), bqkv / sqkv [3 * heads * head_pad], wo [d, heads * head_pad].  head_pad != 64 needs q_prescaled = 0.  `mlp` is the PADDED MLP
      * width the w1 / b1 / s1 / w2 arrays have (zero rows / columns past the true width), a multiple of 128. */
     int head_dim, head_pad;
+    /* register tokens between the CLS row and the patch rows (HF Dinov2WithRegisters: num_register_tokens; needs has_cls).  tokens =
+     * grid^2 + has_cls + registers; token rows of an image: CLS, the registers, the patches.  0 = every tower before 640, unchanged.
+     * With q_prescaled == 2 and 64 n patches such a tower (prefix = 1 + registers <= 8) runs visrep_mhsa_prefix_fwd. */
+    int registers;
 } visrep_vit_config;
 typedef struct {           /* device pointers; matrices bf16 [out,in], vectors fp32; ls1/ls2 NULL when no LayerScale */
     const float *ln1_g, *ln1_b; const void* wqkv; const float* bqkv; const void* wo; const float* bo; const float* ls1;
@@ -283,7 +303,10 @@ typedef struct {           /* device pointers; matrices bf16 [out,in], vectors f
 } visrep_vit_layer;
 typedef struct {
     const void* patch_w;   /* bf16 [d, kpad], zero padded past 3*p*p */
-    const float *patch_b, *cls, *pos, *pre_ln_g, *pre_ln_b;   /* patch_b / cls / pre_ln_* may be NULL */
+    /* patch_b / cls / pre_ln_* may be NULL.  cls: [d], or for a tower with registers the table [1 + registers, d] of the non-patch rows (the
+     * class token, then the register tokens); pos: [tokens, d] in token-row order - a register tower's rows 1 .. registers are ZERO (HF
+     * adds the position embedding before it inserts the registers), so that row r of the embedding is cls[r] + pos[r] for every prefix row. */
+    const float *patch_b, *cls, *pos, *pre_ln_g, *pre_ln_b;
     const visrep_vit_layer* layers;   /* HOST array of `layers` entries */
 } visrep_vit_weights;
 size_t visrep_vit_workspace_bytes(const visrep_vit_config* cfg, int B);

@@ -11,7 +11,7 @@ import threading
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VISREP_LIB") or os.path.join(_PKG, "libvisrep_hip.so")   # VISREP_LIB: diagnostic builds only
 
-ABI_VERSION = 630                 # include/visrep.h VISREP_VERSION this binding was written against (checked at load)
+ABI_VERSION = 640                 # include/visrep.h VISREP_VERSION this binding was written against (checked at load)
 BF16, F32 = 0, 1
 EPI_BIAS, EPI_ACT, EPI_RESID, EPI_VT, EPI_PATCH, EPI_F32 = range(6)
 EPI_GATED = 7
@@ -21,7 +21,7 @@ ACT = {"none": 0, "quick_gelu": 1, "gelu": 2, "gelu_erf": 2, "gelu_tanh": 3, "ge
 class VitConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("image_size", "patch", "d", "heads", "mlp", "layers", "tokens", "has_cls", "pre_ln",
                                        "act", "kpad")] + [("eps", C.c_float), ("q_prescaled", C.c_int), ("head_dim", C.c_int),
-                                                                    ("head_pad", C.c_int)]
+                                                                    ("head_pad", C.c_int), ("registers", C.c_int)]
 
 
 class VitLayer(C.Structure):
@@ -56,6 +56,8 @@ SIGNATURES = {
     "visrep_mhsa_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "visrep_mhsa_cls_supported": (_i, [_i]),
     "visrep_mhsa_cls_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "visrep_mhsa_prefix_supported": (_i, [_i, _i]),
+    "visrep_mhsa_prefix_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "visrep_set_scratch": (_i, [_vp, _sz]),
     "visrep_set_stream_scratch": (_i, [_vp, _vp, _sz]),
     "visrep_layernorm_stats": (_i, [_vp, _i, _vp, _i, _i, _f, _vp]),
@@ -96,6 +98,7 @@ SIGNATURES = {
     "visrep_mean_groups": (_i, [_vp, _vp, _i, _i, _l, _vp]),
     "visrep_im2col": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "visrep_cls_rows": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "visrep_prefix_rows": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "visrep_cast_f32_bf16": (_i, [_vp, _vp, _l, _vp]),
     "visrep_vit_workspace_bytes": (_sz, [C.POINTER(VitConfig), _i]),
     "visrep_vit_forward": (_i, [C.POINTER(VitConfig), C.POINTER(VitWeights), _vp, _i, _vp, _i, _i, _vp, _vp]),
@@ -180,7 +183,7 @@ def load(build_if_missing: bool = True):
         return lib
 
 
-ROUTES = ("gemm_256", "gemm_128", "gemm_tail", "splitk", "conv_256", "conv_128", "conv_128_gn", "attn", "attn_wide", "attn_cls", "conv_halo", "conv_c8", "attn_96")
+ROUTES = ("gemm_256", "gemm_128", "gemm_tail", "splitk", "conv_256", "conv_128", "conv_128_gn", "attn", "attn_wide", "attn_cls", "conv_halo", "conv_c8", "attn_96", "attn_prefix")
 
 
 def xcd_balance() -> dict:

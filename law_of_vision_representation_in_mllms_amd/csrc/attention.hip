@@ -463,6 +463,206 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_cls(const AttnClsArgs p) {
 }
 
 
+// ---- image-aligned self-attention with a short PREFIX of side keys (DINOv2 with registers: CLS + 4 register tokens, T = 5 + 64 n: 261 at
+// 224 px, 581 at 336 px).  attn_fwd_cls with NP side keys instead of one: the patch keys NP .. T-1 of an image are whole tiles (K rows from
+// b T + NP on, V^T columns b (T - NP) + t - NP), the NP prefix keys are the initial state of the online softmax, the queries are all T rows.
+// Tile loop, deferred-maximum rescale, empty-wave path, XCD remap and store tail are attn_fwd_cls's, line for line.  They are a copy and not
+// a shared body: moving attn_fwd_cls's body into a function template that both kernels instantiate changed attn_fwd_cls's generated code
+// (4804 -> 4628 bytes), and that kernel is the headline tower's attention route.
+struct AttnPrefixArgs {
+    const bf16_t* q; const bf16_t* k; const bf16_t* vt; const bf16_t* vcls; bf16_t* out;      // vcls: the V rows of the prefix tokens [B NP, ldvc]
+    int B, T, H, ldq, ldk, ldvt, ldvc, ldo, NP;
+};
+
+__global__ __launch_bounds__(256, 4) void attn_fwd_prefix(const AttnPrefixArgs p) {
+    constexpr int STAGE_B = 2 * TILE_B;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lq = lane & 31, hi = lane >> 5;
+    const int NP = p.NP;
+    const int nqt = (p.T + 127) >> 7, P = p.T - NP, ntile = P >> 6;
+    int id = xcd_remap(blockIdx.x, gridDim.x);
+    const int qt = id % nqt; id /= nqt;
+    const int h = id % p.H;
+    const int b = id / p.H;
+
+    const int qloc = qt * 128 + wave * 32 + lq;
+    const size_t qrow = (size_t)b * p.T + (qloc < p.T ? qloc : p.T - 1);
+    bf16x8 qf[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) qf[kk] = *reinterpret_cast<const bf16x8*>(p.q + qrow * p.ldq + h * 64 + kk * 16 + hi * 8);
+
+    // ---- staging: every tile is full and in range, the cursors only advance
+    const int srow = tid >> 3;
+    const int lslot = (tid & 7) ^ ((srow >> 1) & 7);
+    const bf16_t* kcur = p.k + h * 64 + lslot * 8 + ((size_t)b * p.T + NP + srow) * p.ldk;
+    const bf16_t* vcur = p.vt + (size_t)(h * 64 + srow) * p.ldvt + lslot * 8 + (size_t)b * P;
+    const size_t kstep = (size_t)KT * p.ldk, khalf = (size_t)32 * p.ldk, vhalf = (size_t)32 * p.ldvt;
+    auto stage = [&](int buf) {
+        char* sk = smem + buf * STAGE_B + wave * 1024;
+        char* sv = sk + TILE_B;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) glds16(kcur + j * khalf, sk + j * 4096);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) glds16(vcur + j * vhalf, sv + j * 4096);
+        kcur += kstep; vcur += KT;
+    };
+    const int rsw = (lq >> 1) & 7;
+    const int rbase = lq * 128;
+
+    stage(0);
+    __syncthreads();
+    if (qt * 128 + wave * 32 >= p.T) {                         // an empty wave only stages its share and meets the barriers
+        for (int it = 0; it < ntile; ++it) {
+            if (it + 1 < ntile) stage((it & 1) ^ 1);
+            __syncthreads();
+        }
+        return;
+    }
+
+    // ---- the prefix keys: s_i = q . k_i over this lane's half of the head (d = 16 kk + 8 hi .. + 8), the other half lives in lane ^ 32
+    float m_run, l_run;
+    f32x16 o[2], minit;
+    {
+        // NP side keys (K rows b T .. b T + NP - 1, V rows b NP .. of vcls): s_i as the CLS term below, the reference m = max_i s_i, p_i = 2^(s_i - m)
+        // in fp32 (never rounded to bf16: the side terms do not pass through the matrix pipe), l = sum p_i, O = sum p_i v_i by fp32 FMAs.  The loops
+        // are unrolled to the limit of 8 with a wave-uniform guard, so that the scores stay in registers (no scratch) whatever NP is.
+        const bf16_t* kc = p.k + (size_t)b * p.T * p.ldk + h * 64 + hi * 8;
+        float sc[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            sc[i] = -INFINITY;
+            if (i < NP) {                                     // uniform
+                float dot = 0.f;
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) {
+                    const u32x4 kw = *reinterpret_cast<const u32x4*>(kc + (size_t)i * p.ldk + kk * 16);
+                    const u32x4 qw = __builtin_bit_cast(u32x4, qf[kk]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dot = __builtin_fmaf(bf_lo(qw[e]), bf_lo(kw[e]), __builtin_fmaf(bf_hi(qw[e]), bf_hi(kw[e]), dot));
+                }
+                dot += __shfl_xor(dot, 32);
+                sc[i] = dot;
+            }
+        }
+        m_run = sc[0];
+#pragma unroll
+        for (int i = 1; i < 8; ++i) m_run = fmaxf(m_run, sc[i]);      // sc[i >= NP] = -inf
+        const bf16_t* vc = p.vcls + (size_t)b * NP * p.ldvc + h * 64 + hi * 4;
+        float lsum = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (i < NP) {                                     // uniform
+                const float pi = sc[i] == m_run ? 1.f : __builtin_amdgcn_exp2f(sc[i] - m_run);     // 2^0 is exact by construction
+                lsum = i == 0 ? pi : lsum + pi;
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                    for (int rg = 0; rg < 4; ++rg) {
+                        const u32x2 vw = *reinterpret_cast<const u32x2*>(vc + (size_t)i * p.ldvc + dt * 32 + rg * 8);
+                        const float v0 = bf_lo(vw[0]), v1 = bf_hi(vw[0]), v2 = bf_lo(vw[1]), v3 = bf_hi(vw[1]);
+                        if (i == 0) {
+                            o[dt][4 * rg + 0] = pi * v0; o[dt][4 * rg + 1] = pi * v1; o[dt][4 * rg + 2] = pi * v2; o[dt][4 * rg + 3] = pi * v3;
+                        } else {
+                            o[dt][4 * rg + 0] = __builtin_fmaf(pi, v0, o[dt][4 * rg + 0]); o[dt][4 * rg + 1] = __builtin_fmaf(pi, v1, o[dt][4 * rg + 1]);
+                            o[dt][4 * rg + 2] = __builtin_fmaf(pi, v2, o[dt][4 * rg + 2]); o[dt][4 * rg + 3] = __builtin_fmaf(pi, v3, o[dt][4 * rg + 3]);
+                        }
+                    }
+            }
+        l_run = hi == 0 ? lsum : 0.f;                         // the two halves of a row are added at the end: count the side keys once
+#pragma unroll
+        for (int r = 0; r < 16; ++r) minit[r] = -m_run;
+    }
+
+    for (int it = 0; it < ntile; ++it) {
+        const int cur = it & 1;
+        if (it + 1 < ntile) stage(cur ^ 1);
+        const char* sk = smem + cur * STAGE_B;
+        const char* sv = sk + TILE_B;
+        f32x16 s[2];
+        s[0] = minit; s[1] = minit;                           // the reference is subtracted inside the matrix pipe
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int kt2 = 0; kt2 < 2; ++kt2) {
+                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + kt2 * 4096 + rbase + (((2 * kk + hi) ^ rsw) << 4));
+                s[kt2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], s[kt2], 0, 0, 0);
+            }
+        float mloc = fmaxf(fmaxf(s[0][0], s[0][1]), s[0][2]), mloc1 = fmaxf(fmaxf(s[1][0], s[1][1]), s[1][2]);
+#pragma unroll
+        for (int r = 3; r < 15; r += 2) {
+            mloc = fmaxf(fmaxf(mloc, s[0][r]), s[0][r + 1]);
+            mloc1 = fmaxf(fmaxf(mloc1, s[1][r]), s[1][r + 1]);
+        }
+        mloc = fmaxf(fmaxf(mloc, s[0][15]), fmaxf(mloc1, s[1][15]));
+        {
+            const unsigned u = __builtin_bit_cast(unsigned, mloc);
+            const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+            mloc = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
+        }
+        if (__any(mloc > (float)(VISREP_ATTN_V1_THR > 0 ? VISREP_ATTN_V1_THR : 0))) {     // wave-uniform: some row outgrew the reference by > 2^THR
+            const float delta = fmaxf(mloc, 0.f);
+#pragma unroll
+            for (int kt2 = 0; kt2 < 2; ++kt2)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[kt2][r] -= delta;
+            const float alpha = __builtin_amdgcn_exp2f(-delta);
+            l_run *= alpha;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
+            m_run += delta;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) minit[r] = -m_run;
+        }
+        float psum = 0.f;
+        uint32_t pb[2][8];
+#pragma unroll
+        for (int kt2 = 0; kt2 < 2; ++kt2)
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const float p0 = __builtin_amdgcn_exp2f(s[kt2][r]), p1 = __builtin_amdgcn_exp2f(s[kt2][r + 1]);
+                psum += p0 + p1;
+                pb[kt2][r >> 1] = pack_bf16(p0, p1);
+            }
+        l_run += psum;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const u32x4 w = {pb[c >> 1][4 * (c & 1) + 0], pb[c >> 1][4 * (c & 1) + 1], pb[c >> 1][4 * (c & 1) + 2], pb[c >> 1][4 * (c & 1) + 3]};
+            const bf16x8 pf = __builtin_bit_cast(bf16x8, w);
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) {
+                const bf16x8 vf = *reinterpret_cast<const bf16x8*>(sv + dt * 4096 + rbase + (((2 * c + hi) ^ rsw) << 4));
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[dt], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+
+    l_run += __shfl_xor(l_run, 32);
+    const float inv = 1.f / l_run;
+    bf16_t* orow = p.out + ((size_t)b * p.T + (qloc < p.T ? qloc : p.T - 1)) * p.ldo + h * 64;
+    const bool wide = (p.ldo & 7) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0;          // uniform
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int rg = 0; rg < 4; rg += 2) {
+            u32x2 a = {pack_bf16(o[dt][4 * rg + 0] * inv, o[dt][4 * rg + 1] * inv), pack_bf16(o[dt][4 * rg + 2] * inv, o[dt][4 * rg + 3] * inv)};
+            u32x2 c = {pack_bf16(o[dt][4 * rg + 4] * inv, o[dt][4 * rg + 5] * inv), pack_bf16(o[dt][4 * rg + 6] * inv, o[dt][4 * rg + 7] * inv)};
+            if (wide) {
+                const auto w0 = __builtin_amdgcn_permlane32_swap(a[0], c[0], false, false);
+                const auto w1 = __builtin_amdgcn_permlane32_swap(a[1], c[1], false, false);
+                if (qloc < p.T) {
+                    const u32x4 q4 = {(unsigned)w0[0], (unsigned)w1[0], (unsigned)w0[1], (unsigned)w1[1]};
+                    *reinterpret_cast<u32x4*>(orow + dt * 32 + (rg + hi) * 8) = q4;
+                }
+            } else if (qloc < p.T) {
+                *reinterpret_cast<u32x2*>(orow + dt * 32 + rg * 8 + hi * 4) = a;
+                *reinterpret_cast<u32x2*>(orow + dt * 32 + (rg + 1) * 8 + hi * 4) = c;
+            }
+        }
+}
+
+
 // ---- head width 96 (true widths 65 .. 96 zero-padded by the weight packer: SigLIP-so400m 72, ViT-H/14 80, ViT-g/14 88, DiT 72).  The flash
 // loop of attn_fwd (plain scale, deferred running maximum) with six 16-wide k-slices for Q.K^T and three 32-wide O tiles for P.V: 18 MFMAs
 // per 64-key tile where the 128-padded route runs 24 (a true-72 head: 25 % of the matrix work on padding instead of 44 %), 24 Q registers
@@ -862,7 +1062,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_wide(const AttnArgs p) {
 
 }  // namespace
 
-// global_load_lds and the bf16x8 Q loads move 16 bytes per lane (q, k, vt); the narrow store path and the CLS value rows move 8 (out, vcls)
+// global_load_lds and the bf16x8 Q loads move 16 bytes per lane (q, k, vt); the narrow store path and the CLS / prefix value rows move 8 (out, vcls, vpre)
 static bool attn_misaligned(uintptr_t mask, const void* a, const void* b = nullptr, const void* c = nullptr) {
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & mask) != 0;
 }
@@ -964,6 +1164,31 @@ extern "C" int visrep_mhsa_cls_fwd(const void* qk, int ldqk, const void* vt, int
     visrep_count_route(VISREP_ROUTE_ATTN_CLS);
     hipLaunchKernelGGL(attn_fwd_cls, dim3(((T + 127) / 128) * H * B), dim3(256), (size_t)4 * TILE_B, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : visrep_set_error(VISREP_ERR_LAUNCH, "mhsa_cls: launch failed");
+}
+
+extern "C" int visrep_mhsa_prefix_supported(int T, int NP) { return NP >= 1 && NP <= 8 && T - NP >= 64 && (T - NP) % 64 == 0 ? 1 : 0; }
+
+// Image-aligned self-attention with NP side keys per image (attn_fwd_prefix): qk as for visrep_mhsa_fwd with pre-scaled Q; vt = V^T of the
+// PATCH tokens, column b (T - NP) + perm16(t - NP); vpre = the V projection of the prefix rows [B NP, ldvp], row b NP + i.
+extern "C" int visrep_mhsa_prefix_fwd(const void* qk, int ldqk, const void* vt, int ldvt, const void* vpre, int ldvp, void* out, int ldo, int B, int T,
+                                      int NP, int H, int head_dim, void* stream) {
+    if (NP < 1 || NP > 8) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_prefix: the prefix must be 1 .. 8 tokens");
+    if (head_dim != 64) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_prefix: only head_dim 64 is implemented");
+    if (!qk || !vt || !vpre || !out) return visrep_set_error(VISREP_ERR_ARG, "mhsa_prefix: null pointer");
+    if (attn_misaligned(15, qk, vt)) return visrep_set_error(VISREP_ERR_ARG, "mhsa_prefix: qk and vt must be 16-byte aligned");
+    if (attn_misaligned(7, vpre, out)) return visrep_set_error(VISREP_ERR_ARG, "mhsa_prefix: vpre and out must be 8-byte aligned");
+    if (B <= 0 || H <= 0 || !visrep_mhsa_prefix_supported(T, NP))
+        return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_prefix: needs T = prefix + a multiple of 64 (side keys + full key tiles)");
+    if ((ldqk % 8) || (ldvt % 64) || (ldo % 4) || (ldvp % 4)) return visrep_set_error(VISREP_ERR_SHAPE, "attention: bad leading dimension");
+    if (ldqk < 2 * H * 64) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_prefix: ldqk must cover Q | K (2 H 64 columns)");
+    if ((long)ldvt < (long)B * (T - NP)) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_prefix: ldvt must cover B (T - prefix) columns");
+    if (ldvp < H * 64) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_prefix: ldvp must cover H * 64 columns");
+    AttnPrefixArgs a;
+    a.q = (const bf16_t*)qk; a.k = (const bf16_t*)qk + (size_t)H * 64; a.vt = (const bf16_t*)vt; a.vcls = (const bf16_t*)vpre; a.out = (bf16_t*)out;
+    a.B = B; a.T = T; a.H = H; a.ldq = ldqk; a.ldk = ldqk; a.ldvt = ldvt; a.ldvc = ldvp; a.ldo = ldo; a.NP = NP;
+    visrep_count_route(VISREP_ROUTE_ATTN_PREFIX);
+    hipLaunchKernelGGL(attn_fwd_prefix, dim3(((T + 127) / 128) * H * B), dim3(256), (size_t)4 * TILE_B, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : visrep_set_error(VISREP_ERR_LAUNCH, "mhsa_prefix: launch failed");
 }
 
 extern "C" int visrep_mhsa_fwd(const void* qk, int ldqk, const void* vt, int ldvt, void* out, int ldo,

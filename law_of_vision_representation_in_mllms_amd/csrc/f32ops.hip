@@ -685,7 +685,8 @@ __global__ void im2col_f32_kernel(const float* __restrict__ px, float* __restric
     }
 }
 
-// token rows of the embedding: x[b, cls_off + p] = patches[b * P + p] + pos[cls_off + p];  x[b, 0] = cls + pos[0] (CLS towers)
+// token rows of the embedding: x[b, cls_off + p] = patches[b * P + p] + pos[cls_off + p];  x[b, t] = cls[t] + pos[t] for the cls_off prefix rows (CLS
+// towers: the class token; towers with registers: cls is the table [1 + registers, d] and the registers' pos rows are zero)
 __global__ void embed_finish_f32_kernel(const float* __restrict__ patches, const float* __restrict__ cls, const float* __restrict__ pos,
                                         float* __restrict__ x, int B, int T, int P, int d) {
     const int cls_off = T - P;
@@ -695,7 +696,7 @@ __global__ void embed_finish_f32_kernel(const float* __restrict__ patches, const
         const long bt = i / d;
         const int b = (int)(bt / T), t = (int)(bt % T);
         const float pv = pos[(size_t)t * d + c];
-        x[i] = (t < cls_off) ? cls[c] + pv : patches[((size_t)b * P + (t - cls_off)) * d + c] + pv;
+        x[i] = (t < cls_off) ? cls[(size_t)t * d + c] + pv : patches[((size_t)b * P + (t - cls_off)) * d + c] + pv;
     }
 }
 
@@ -802,7 +803,7 @@ WsF32 layout_f32(const visrep_vit_config* c, int B) {
     w.qkv = off; off += up256(M * 3 * c->d * 4);
     w.sc = off;  off += up256((size_t)B * c->heads * c->tokens * w.lds * 4);
     const size_t mlp_b = M * c->mlp * 4 * (is_swiglu(c) ? 3 : 1);          // SwiGLU: the hidden [M, mlp], then fc1's [M, 2 mlp] output
-    const size_t P = (size_t)c->tokens - c->has_cls;
+    const size_t P = (size_t)c->tokens - c->has_cls - c->registers;
     const size_t emb_b = up256((size_t)B * P * c->kpad * 4) + (size_t)B * P * c->d * 4;    // im2col columns + patch rows alias the MLP buffer
     w.mlp = off; off += up256(mlp_b > emb_b ? mlp_b : emb_b);
     w.total = off;
@@ -819,7 +820,7 @@ WsF32X layout_f32x(const visrep_vit_config* c, int B) {
     w.hp = off;  off += up256(M * 3 * c->d * 2);
     w.qkv = off; off += up256(M * 3 * c->d * 4);
     const size_t mlp_b = M * 3 * c->mlp * 2 + (is_swiglu(c) ? M * 2 * c->mlp * 4 : 0);   // SwiGLU: fc1's fp32 [M, 2 mlp] output behind the planes
-    const size_t P = (size_t)c->tokens - c->has_cls;
+    const size_t P = (size_t)c->tokens - c->has_cls - c->registers;
     const size_t emb_b = up256((size_t)B * P * c->kpad * 4) + (size_t)B * P * c->d * 4;
     w.mlpp = off; off += up256(mlp_b > emb_b ? mlp_b : emb_b);
     w.total = off;
@@ -955,7 +956,8 @@ extern "C" int visrep_vit_forward_f32(const visrep_vit_config* c, const visrep_v
     if (c->d % c->heads || (c->d / c->heads) % 4 || c->d % 4 || c->mlp % 4 || c->kpad % 4)
         return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32: d, head width, mlp and kpad must be multiples of 4");
     const int grid = c->image_size / c->patch;
-    if (grid * grid + (c->has_cls ? 1 : 0) != c->tokens) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32: tokens != grid^2 + cls");
+    if (c->registers < 0 || (c->registers > 0 && !c->has_cls)) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32: register tokens need a CLS token");
+    if (grid * grid + (c->has_cls ? 1 : 0) + c->registers != c->tokens) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32: tokens != grid^2 + cls + registers");
     hipStream_t s = (hipStream_t)stream;
     const WsF32 L = layout_f32(c, B);
     char* base = (char*)workspace;
@@ -1042,7 +1044,8 @@ extern "C" int visrep_vit_forward_f32_split(const visrep_vit_config* c, const vi
     if (n_layers < 0 || n_layers > c->layers) return visrep_set_error(VISREP_ERR_ARG, "vit_forward_f32_split: n_layers out of range");
     if (!split_route_supported(c)) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32_split: d and mlp must be multiples of 256, head width 64");
     const int grid = c->image_size / c->patch;
-    if (grid * grid + (c->has_cls ? 1 : 0) != c->tokens) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32_split: tokens != grid^2 + cls");
+    if (c->registers < 0 || (c->registers > 0 && !c->has_cls)) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32_split: register tokens need a CLS token");
+    if (grid * grid + (c->has_cls ? 1 : 0) + c->registers != c->tokens) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32_split: tokens != grid^2 + cls + registers");
     hipStream_t s = (hipStream_t)stream;
     const WsF32X L = layout_f32x(c, B);
     char* base = (char*)workspace;

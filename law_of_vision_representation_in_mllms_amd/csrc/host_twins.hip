@@ -115,7 +115,8 @@ extern "C" int visrep_vit_forward_cpu(const visrep_vit_config* c, const visrep_v
     if (c->heads <= 0 || c->d % c->heads) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_cpu: d must be a multiple of heads");
     const int grid = c->image_size / c->patch, P = grid * grid, T = c->tokens, d = c->d, p = c->patch, S = c->image_size;
     // S / patch floors like Conv2d(k = s = patch): trailing pixels fill no patch (384 / 14 = 27)
-    if (grid <= 0 || P + (c->has_cls ? 1 : 0) != T) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_cpu: tokens != grid^2 + cls");
+    if (c->registers < 0 || (c->registers > 0 && !c->has_cls)) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_cpu: register tokens need a CLS token");
+    if (grid <= 0 || P + (c->has_cls ? 1 : 0) + c->registers != T) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_cpu: tokens != grid^2 + cls + registers");
     const int kp = 3 * p * p, kpad = c->kpad > 0 ? c->kpad : kp;       // patch_w rows are kpad floats wide (zero padded past 3 p p)
     if (kpad < kp) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_cpu: kpad < 3 * patch^2");
     const long M = (long)B * T;
@@ -132,13 +133,14 @@ extern "C" int visrep_vit_forward_cpu(const visrep_vit_config* c, const visrep_v
     });
     std::vector<float> emb((size_t)B * P * d);
     linear_rows(cols.data(), kp, pw, kpad, w->patch_b, emb.data(), d, (long)B * P, d, kp, threads);
-    const int off = c->has_cls ? 1 : 0;
+    const int off = (c->has_cls ? 1 : 0) + c->registers;      // prefix rows: the class token, then the registers (cls = [off, d], their pos rows zero)
     parallel_for(M, threads, [&](long r) {
         const int b = (int)(r / T), t = (int)(r % T);
         float* x = hidden + (size_t)r * d;
         const float* pos = w->pos + (size_t)t * d;
-        if (c->has_cls && t == 0) {
-            for (int i = 0; i < d; ++i) x[i] = w->cls[i] + pos[i];
+        if (t < off) {
+            const float* pre = w->cls + (size_t)t * d;
+            for (int i = 0; i < d; ++i) x[i] = pre[i] + pos[i];
         } else {
             const float* e = emb.data() + ((size_t)b * P + (t - off)) * d;
             for (int i = 0; i < d; ++i) x[i] = e[i] + pos[i];

@@ -157,6 +157,13 @@ __global__ void cls_rows(bf16_t* __restrict__ x, int ldx, const float* __restric
     for (int n = threadIdx.x; n < d; n += blockDim.x) x[(size_t)b * T * ldx + n] = f2bf(cls[n] + pos[n]);
 }
 
+// x[b*T + r][:] = table[r] + pos[r], r < prefix (the class token and the register tokens; the registers' pos rows are zero)
+__global__ void prefix_rows(bf16_t* __restrict__ x, int ldx, const float* __restrict__ table, const float* __restrict__ pos,
+                            int B, int T, int d) {
+    const int b = blockIdx.x, r = blockIdx.y;
+    for (int n = threadIdx.x; n < d; n += blockDim.x) x[((size_t)b * T + r) * ldx + n] = f2bf(table[(size_t)r * d + n] + pos[(size_t)r * d + n]);
+}
+
 __global__ void cast_f32_to_bf16(const float* __restrict__ src, bf16_t* __restrict__ dst, long n) {
     for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 2; i < n; i += (long)gridDim.x * blockDim.x * 2) {
         if (i + 1 < n) *reinterpret_cast<uint32_t*>(dst + i) = pack_bf16(src[i], src[i + 1]);
@@ -212,6 +219,15 @@ extern "C" int visrep_cls_rows(void* x, int ldx, const float* cls, const float* 
     if (B <= 0) return 0;
     hipLaunchKernelGGL(cls_rows, dim3(B), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, ldx, cls, pos, B, T, d);
     return hipGetLastError() == hipSuccess ? 0 : visrep_set_error(VISREP_ERR_LAUNCH, "cls_rows: launch failed");
+}
+
+extern "C" int visrep_prefix_rows(void* x, int ldx, const float* table, const float* pos, int B, int T, int prefix, int d, void* stream) {
+    if (B <= 0) return 0;
+    if (!x || !table || !pos) return visrep_set_error(VISREP_ERR_ARG, "prefix_rows: null pointer");
+    if (prefix < 1 || prefix > T || B > 65535) return visrep_set_error(VISREP_ERR_SHAPE, "prefix_rows: 1 <= prefix <= T");
+    if (prefix == 1) return visrep_cls_rows(x, ldx, table, pos, B, T, d, stream);
+    hipLaunchKernelGGL(prefix_rows, dim3(B, prefix), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, ldx, table, pos, B, T, d);
+    return hipGetLastError() == hipSuccess ? 0 : visrep_set_error(VISREP_ERR_LAUNCH, "prefix_rows: launch failed");
 }
 
 extern "C" int visrep_cast_f32_bf16(const float* src, void* dst, long n, void* stream) {

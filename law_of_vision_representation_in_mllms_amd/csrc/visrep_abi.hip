@@ -320,11 +320,11 @@ Ws layout(const visrep_vit_config* c, int B) {
     w.h = off;   off += up(Mp * dh * 2, 256);                       // LayerNorm output [M, d] / attention output [M, da]
     w.qk = off;  off += up(Mp * 2 * da * 2, 256);
     w.vt = off;  off += up(da * w.ldvt * 2, 256);
-    w.vcls = off; off += up((size_t)B * da * 2, 256);               // V rows of the CLS tokens (image-aligned attention)
+    w.vcls = off; off += up((size_t)B * (1 + (c->registers > 0 ? c->registers : 0)) * da * 2, 256);   // V rows of the CLS (and register) tokens (image-aligned attention)
     // SwiGLU towers: the gated fc1 writes [Mp, mlp] like every other activation; the unfused A/B route (visrep_set_fuse_gate(0)) keeps the
     // [Mp, 2 mlp] GEMM output in front of it
     const size_t mlp_b = Mp * c->mlp * 2 * ((c->act == VISREP_ACT_SWIGLU && !t_visrep_fuse_gate) ? 3 : 1);
-    const size_t cols_b = up((size_t)B * (c->tokens - c->has_cls), 128) * c->kpad * 2;
+    const size_t cols_b = up((size_t)B * (c->tokens - c->has_cls - c->registers), 128) * c->kpad * 2;
     w.mlp = off; off += up(mlp_b > cols_b ? mlp_b : cols_b, 256);   // im2col columns alias the MLP buffer
     w.rt = off;  off += up((Mp + 8) * sizeof(float2), 256);         // folded-LayerNorm row statistics (zero past M)
     w.part = off; off += up(Mp * (c->d / 64) * sizeof(float2), 256);  // per-row partial sums left by the residual GEMM epilogues
@@ -354,7 +354,10 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
     if (c->d % 128 || c->mlp % 128 || c->kpad % 64)
         return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: d, mlp % 128 and kpad % 64 required (mlp = the zero-padded MLP width)");
     const int grid = c->image_size / c->patch;
-    if (grid * grid + (c->has_cls ? 1 : 0) != c->tokens) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: tokens != grid^2 + cls");
+    if (c->registers < 0 || (c->registers > 0 && !c->has_cls)) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: register tokens need a CLS token (registers >= 0)");
+    const int prefix = (c->has_cls ? 1 : 0) + c->registers;       // non-patch rows in front of every image's patches
+    if (grid * grid + prefix != c->tokens) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: tokens != grid^2 + cls + registers");
+    if (c->has_cls && !w->cls) return visrep_set_error(VISREP_ERR_ARG, "vit_forward: a CLS tower needs the cls table");
     if (c->act < VISREP_ACT_NONE || c->act > VISREP_ACT_SWIGLU) return visrep_set_error(VISREP_ERR_ARG, "vit_forward: unknown activation code");
     hipStream_t s = (hipStream_t)stream;
     const Ws L = layout(c, B);
@@ -373,9 +376,10 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
     GemmArgs g{};
     g.A = mlp; g.lda = c->kpad; g.W = (const bf16_t*)w->patch_w; g.ldw = c->kpad; g.C = x; g.ldc = d;
     g.bias = w->patch_b; g.pos = w->pos; g.M = B * P; g.N = d; g.K = c->kpad; g.epi = EPI_PATCH;
-    g.patches = P; g.tokens = T; g.cls_off = c->has_cls ? 1 : 0;
+    g.patches = P; g.tokens = T; g.cls_off = prefix;
     VR_TRY(visrep_gemm_dispatch(g, s));
-    if (c->has_cls) VR_TRY(visrep_cls_rows(x, d, w->cls, w->pos, B, T, d, stream));
+    if (prefix == 1) VR_TRY(visrep_cls_rows(x, d, w->cls, w->pos, B, T, d, stream));
+    else if (prefix > 1) VR_TRY(visrep_prefix_rows(x, d, w->cls, w->pos, B, T, prefix, d, stream));
     if (c->pre_ln) VR_TRY(visrep_layernorm(x, d, w->pre_ln_g, w->pre_ln_b, x, d, M, d, c->eps, stream));
 
     // V^T columns past B*T are read (with zero softmax weight) by the last key tile: keep them finite
@@ -388,7 +392,10 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
     const float scale = c->q_prescaled ? 0.f : 1.f / sqrtf((float)hd);   // the TRUE head_dim^-0.5 (64: 0.125 exactly); 0 = folded into the Q weights (attn_fwd PS)
     // Image-aligned attention (attn_fwd_cls): the patch tokens of an image are whole key tiles and the CLS key is a side term, so V is
     // projected by two row-mapped GEMMs - the patch rows into V^T (column b (T - 1) + t - 1), the CLS rows into vcls [B, d]
-    const bool aligned = c->q_prescaled >= 2 && dp == 64 && hd == 64 && c->has_cls && visrep_mhsa_cls_supported(T) && t_visrep_attn_variant == 1;
+    const bool side = c->q_prescaled >= 2 && dp == 64 && hd == 64 && t_visrep_attn_variant == 1;
+    const bool aligned = side && prefix == 1 && visrep_mhsa_cls_supported(T);
+    // the same with CLS + registers as a prefix of side keys (attn_fwd_prefix): patch rows -> V^T column b P + t - prefix, prefix rows -> vcls [B prefix, d]
+    const bool aligned_pre = side && prefix >= 2 && visrep_mhsa_prefix_supported(T, prefix);
     bool rt_ready = false;        // rt already holds the statistics of x (left by the previous layer's fc2 GEMM)
     for (int l = 0; l < n_layers; ++l) {
         const visrep_vit_layer& W = w->layers[l];
@@ -416,6 +423,13 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
             v.M = B; v.a_period = 1; v.a_first = 0; v.C = vcls; v.ldc = d; v.epi = EPI_BIAS;
             VR_TRY(visrep_gemm_dispatch(v, s));
             VR_TRY(visrep_mhsa_cls_fwd(qk, 2 * d, vt, L.ldvt, vcls, d, h, d, B, T, c->heads, 64, stream));
+        } else if (aligned_pre) {
+            GemmArgs v = a;
+            v.M = B * P; v.a_period = P; v.a_stride = T; v.a_first = prefix;
+            VR_TRY(visrep_gemm_dispatch(v, s));
+            v.M = B * prefix; v.a_period = prefix; v.a_first = 0; v.C = vcls; v.ldc = d; v.epi = EPI_BIAS;
+            VR_TRY(visrep_gemm_dispatch(v, s));
+            VR_TRY(visrep_mhsa_prefix_fwd(qk, 2 * d, vt, L.ldvt, vcls, d, h, d, B, T, prefix, c->heads, 64, stream));
         } else {
             VR_TRY(visrep_gemm_dispatch(a, s));
             VR_TRY(visrep_mhsa_fwd(qk, 2 * da, vt, L.ldvt, h, da, B, T, c->heads, dp, scale, stream));

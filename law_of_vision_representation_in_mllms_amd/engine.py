@@ -10,7 +10,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
-from .vit_weights import ViTSpec
+from .vit_weights import ViTSpec, prefix_table
 
 
 def _round_up(v: int, a: int) -> int:
@@ -145,7 +145,8 @@ class VitEngine:
         if weights["pos"].shape[0] != spec.tokens:
             raise ValueError(f"position embedding has {weights['pos'].shape[0]} rows, spec wants {spec.tokens}")
         self._patch_w = mat(pw)
-        self._vecs = {k: vec(weights.get(k)) for k in ("patch_b", "cls", "pos", "pre_ln_g", "pre_ln_b")}
+        self._vecs = {k: vec(weights.get(k)) for k in ("patch_b", "pos", "pre_ln_g", "pre_ln_b")}
+        self._vecs["cls"] = vec(prefix_table(spec, weights))      # [d], or [1 + registers, d]: the class token, then the register tokens
         n = len(weights["layers"])
         self.n_layers = n
         self._layers = (_lib.VitLayer * max(n, 1))()
@@ -201,7 +202,7 @@ class VitEngine:
         self._w.layers = C.cast(self._layers, C.POINTER(_lib.VitLayer))
         self._cfg = _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, self.mlp_pad, n, spec.tokens,
                                    int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), self._q_mode,
-                                   self.head_dim, self.head_pad)
+                                   self.head_dim, self.head_pad, spec.registers)
         self._ws: Dict[int, torch.Tensor] = {}
         self._pinned = set()                 # batch sizes whose workspace a captured HIP graph refers to
 
@@ -287,7 +288,8 @@ class VitEngineF32:
         if weights["pos"].shape[0] != spec.tokens:
             raise ValueError(f"position embedding has {weights['pos'].shape[0]} rows, spec wants {spec.tokens}")
         self._patch_w = f32(pw)
-        self._vecs = {k: f32(weights.get(k)) for k in ("patch_b", "cls", "pos", "pre_ln_g", "pre_ln_b")}
+        self._vecs = {k: f32(weights.get(k)) for k in ("patch_b", "pos", "pre_ln_g", "pre_ln_b")}
+        self._vecs["cls"] = f32(prefix_table(spec, weights))      # [d], or [1 + registers, d]: the class token, then the register tokens
         n = len(weights["layers"])
         self.n_layers = n
         self._layers = (_lib.VitLayer * max(n, 1))()
@@ -304,7 +306,7 @@ class VitEngineF32:
             setattr(self._w, k, 0 if v is None else v.data_ptr())
         self._w.layers = C.cast(self._layers, C.POINTER(_lib.VitLayer))
         self._cfg = _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, spec.mlp, n, spec.tokens,
-                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps))
+                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), registers=spec.registers)
         self._ws: Dict[int, torch.Tensor] = {}
         self._pinned = set()                 # batch sizes whose workspace a captured HIP graph refers to
         import os
@@ -446,7 +448,8 @@ class VitEngineCPU:
             raise ValueError(f"position embedding has {weights['pos'].shape[0]} rows, spec wants {spec.tokens}")
         self.kpad = 3 * spec.patch * spec.patch
         self._patch_w = f32(weights["patch_w"].reshape(spec.d, -1)[:, : self.kpad])
-        self._vecs = {k: f32(weights.get(k)) for k in ("patch_b", "cls", "pos", "pre_ln_g", "pre_ln_b")}
+        self._vecs = {k: f32(weights.get(k)) for k in ("patch_b", "pos", "pre_ln_g", "pre_ln_b")}
+        self._vecs["cls"] = f32(prefix_table(spec, weights))      # [d], or [1 + registers, d]: the class token, then the register tokens
         n = len(weights["layers"])
         self.n_layers = n
         self._layers = (_lib.VitLayer * max(n, 1))()
@@ -463,7 +466,7 @@ class VitEngineCPU:
             setattr(self._w, k, 0 if v is None else v.data_ptr())
         self._w.layers = C.cast(self._layers, C.POINTER(_lib.VitLayer))
         self._cfg = _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, spec.mlp, n, spec.tokens,
-                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps))
+                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), registers=spec.registers)
 
     @torch.no_grad()
     def forward(self, pixels: torch.Tensor, n_layers: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -674,4 +677,19 @@ def mhsa_cls(qk: torch.Tensor, vt: torch.Tensor, vcls: torch.Tensor, B: int, T: 
     rc = lib.visrep_mhsa_cls_fwd(_lib.ptr(qk), qk.stride(0), _lib.ptr(vt), vt.stride(0), _lib.ptr(vcls), vcls.stride(0), _lib.ptr(out),
                                  out.stride(0), B, T, H, 64, _lib.stream_ptr())
     _lib.check(rc, "visrep_mhsa_cls_fwd")
+    return out
+
+
+def mhsa_prefix_supported(T: int, prefix: int) -> bool:
+    return bool(_lib.load().visrep_mhsa_prefix_supported(int(T), int(prefix)))
+
+
+def mhsa_prefix(qk: torch.Tensor, vt: torch.Tensor, vpre: torch.Tensor, B: int, T: int, prefix: int, H: int) -> torch.Tensor:
+    """Image-aligned self-attention with `prefix` side keys per image (visrep_mhsa_prefix_fwd): qk [B T, 2 H 64] with pre-scaled Q; vt = V^T of
+    the patch tokens (column b (T - prefix) + t - prefix); vpre = V rows of the prefix tokens [B prefix, H 64]."""
+    lib = _lib.require_gpu()
+    out = torch.empty(B * T, H * 64, dtype=torch.bfloat16, device=qk.device)
+    rc = lib.visrep_mhsa_prefix_fwd(_lib.ptr(qk), qk.stride(0), _lib.ptr(vt), vt.stride(0), _lib.ptr(vpre), vpre.stride(0), _lib.ptr(out),
+                                    out.stride(0), B, T, prefix, H, 64, _lib.stream_ptr())
+    _lib.check(rc, "visrep_mhsa_prefix_fwd")
     return out

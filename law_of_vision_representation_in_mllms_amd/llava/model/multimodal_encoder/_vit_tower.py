@@ -182,10 +182,13 @@ class HipViTTower(nn.Module):
     # ------------------------------------------------------------------ reference protocol
     def feature_select(self, image_forward_outs):
         image_features = image_forward_outs.hidden_states[self.select_layer]
+        # Register tokens (DINOv2 with registers) are never features: 'patch' drops the whole prefix, 'cls_patch' keeps the CLS row and drops the
+        # registers, as HF's own backbone and classifier do (`[:, 1 + num_register_tokens:]`).  Without registers this is the reference's `[:, 1:]`.
+        reg = getattr(getattr(self, "spec", None), "registers", 0)
         if self.select_feature == "patch":
-            image_features = image_features[:, 1:]
+            image_features = image_features[:, 1 + reg:]
         elif self.select_feature == "cls_patch":
-            image_features = image_features
+            image_features = torch.cat([image_features[:, :1], image_features[:, 1 + reg:]], dim=1) if reg else image_features
         else:
             raise ValueError(f"Unexpected select feature: {self.select_feature}")
         return image_features

@@ -7,7 +7,9 @@ engine consumes ONE packed layout for all of them; this module converts HF
 PRNG (`numpy.random.RandomState`) when no checkpoint is available offline.
 
 Packed layout (fp32 torch tensors on CPU):
-  patch_w [d, 3*p*p]  patch_b [d]|None  cls [d]|None  pos [T, d]
+  patch_w [d, 3*p*p]  patch_b [d]|None  cls [d]|None  pos [T, d]  reg [R, d] (towers with register tokens only)
+  Token rows of a register tower (HF Dinov2WithRegisters): CLS, the R registers, the patches.  HF adds the position embedding BEFORE it
+  inserts the registers, so `pos` [T, d] carries R zero rows after row 0; `pos_native` stays in the checkpoint's own [1 + n^2, d] form.
   pre_ln_g / pre_ln_b [d]|None
   layers[i]: ln1_g ln1_b wqkv[3d,d] bqkv[3d] wo[d,d] bo[d] ls1[d]|None
              ln2_g ln2_b w1[m,d] b1[m] w2[d,m] b2[d] ls2[d]|None
@@ -40,6 +42,11 @@ class ViTSpec:
     layerscale: bool    # DINOv2
     family: str         # clip | dinov2 | siglip
     pos_grid: int = 0   # native position-embedding grid (DINOv2: 37); 0 = image_size // patch
+    registers: int = 0  # register tokens between the CLS row and the patch rows (HF Dinov2WithRegisters: num_register_tokens)
+
+    def __post_init__(self):
+        if self.registers < 0 or (self.registers > 0 and not self.has_cls):
+            raise ValueError("register tokens need a CLS token (registers >= 0, has_cls)")
 
     @property
     def fc1_rows(self) -> int:
@@ -54,8 +61,13 @@ class ViTSpec:
         return self.grid * self.grid
 
     @property
+    def prefix(self) -> int:
+        """Non-patch rows in front of every image's patch rows: the CLS token and the registers."""
+        return (1 if self.has_cls else 0) + self.registers
+
+    @property
     def tokens(self) -> int:
-        return self.num_patches + (1 if self.has_cls else 0)
+        return self.num_patches + self.prefix
 
     def at_resolution(self, image_size: int) -> "ViTSpec":
         return replace(self, image_size=image_size)
@@ -84,6 +96,12 @@ SPECS: Dict[str, ViTSpec] = {
     # the reference registry either; as recalled from the public config, a local `config.json` wins.
     "facebook/dinov2-giant": ViTSpec("facebook/dinov2-giant", 224, 14, 1536, 40, 24, 4096,
                                      "swiglu", 1e-6, True, False, True, True, "dinov2", pos_grid=37),
+    # DINOv2 with registers (HF Dinov2WithRegisters): four register tokens between the CLS row and the patch rows, otherwise the shapes of
+    # dinov2-large / dinov2-giant.  As recalled from the public configs; a local `config.json` wins.
+    "facebook/dinov2-with-registers-large": ViTSpec("facebook/dinov2-with-registers-large", 224, 14, 1024, 24, 16, 4096,
+                                                    "gelu", 1e-6, True, False, True, True, "dinov2", pos_grid=37, registers=4),
+    "facebook/dinov2-with-registers-giant": ViTSpec("facebook/dinov2-with-registers-giant", 224, 14, 1536, 40, 24, 4096,
+                                                    "swiglu", 1e-6, True, False, True, True, "dinov2", pos_grid=37, registers=4),
 }
 
 
@@ -93,12 +111,12 @@ def swiglu_hidden(d: int, mlp_ratio: float) -> int:
 
 
 def tiny_spec(family: str, act: Optional[str] = None, image_size: int = 28, patch: int = 7, d: int = 64,
-              layers: int = 3, heads: int = 2, mlp: int = 128) -> ViTSpec:
+              layers: int = 3, heads: int = 2, mlp: int = 128, registers: int = 0) -> ViTSpec:
     """Small spec of a given family for fixtures / tests."""
     base = {"clip": SPECS["openai/clip-vit-large-patch14"], "dinov2": SPECS["facebook/dinov2-large"],
             "siglip": SPECS["google/siglip-base-patch16-224"]}[family]
     return replace(base, name=f"tiny-{family}", image_size=image_size, patch=patch, d=d, layers=layers,
-                   heads=heads, mlp=mlp, act=act or base.act, pos_grid=0)
+                   heads=heads, mlp=mlp, act=act or base.act, pos_grid=0, registers=registers)
 
 
 def spec_from_hf_config(cfg, name: str = "", crop_size: Optional[int] = None) -> ViTSpec:
@@ -120,11 +138,14 @@ def spec_from_hf_config(cfg, name: str = "", crop_size: Optional[int] = None) ->
                        cfg.num_attention_heads, cfg.intermediate_size, act, cfg.layer_norm_eps,
                        True, True, False, False, "clip")
     if mt.startswith("dinov2"):
+        if mt not in ("dinov2", "dinov2_with_registers"):
+            raise ValueError(f"unsupported HF model_type {mt!r}")
+        registers = int(cfg.num_register_tokens) if mt == "dinov2_with_registers" else 0
         swiglu = bool(getattr(cfg, "use_swiglu_ffn", False))     # giant: gated MLP, hidden_act is not used by it
         mlp = swiglu_hidden(cfg.hidden_size, cfg.mlp_ratio) if swiglu else int(cfg.hidden_size * cfg.mlp_ratio)
         return ViTSpec(name, int(crop_size or 224), cfg.patch_size, cfg.hidden_size, cfg.num_hidden_layers,
                        cfg.num_attention_heads, mlp, "swiglu" if swiglu else act, cfg.layer_norm_eps,
-                       True, False, True, True, "dinov2", pos_grid=cfg.image_size // cfg.patch_size)
+                       True, False, True, True, "dinov2", pos_grid=cfg.image_size // cfg.patch_size, registers=registers)
     if mt.startswith("siglip"):
         return ViTSpec(name, cfg.image_size, cfg.patch_size, cfg.hidden_size, cfg.num_hidden_layers,
                        cfg.num_attention_heads, cfg.intermediate_size, act, cfg.layer_norm_eps,
@@ -143,8 +164,9 @@ def _strip(sd: Dict[str, torch.Tensor], prefixes) -> Dict[str, torch.Tensor]:
     return out
 
 
-def interpolate_pos(pos: torch.Tensor, has_cls: bool, grid: int) -> torch.Tensor:
-    """Bicubic position-embedding resize (HF Dinov2Embeddings.interpolate_pos_encoding, size= form, fp32)."""
+def interpolate_pos(pos: torch.Tensor, has_cls: bool, grid: int, antialias: bool = False) -> torch.Tensor:
+    """Bicubic position-embedding resize (HF Dinov2Embeddings.interpolate_pos_encoding, size= form, fp32).  `pos` is the checkpoint's own
+    table [has_cls + n^2, d] (no register rows).  antialias: HF Dinov2WithRegistersEmbeddings resizes with antialias=True, plain Dinov2 without."""
     cls = pos[:1] if has_cls else pos[:0]
     patch = pos[1:] if has_cls else pos
     n = int(round(patch.shape[0] ** 0.5))
@@ -152,9 +174,19 @@ def interpolate_pos(pos: torch.Tensor, has_cls: bool, grid: int) -> torch.Tensor
         return pos
     d = pos.shape[-1]
     pp = patch.reshape(1, n, n, d).permute(0, 3, 1, 2).float()
-    pp = torch.nn.functional.interpolate(pp, size=(grid, grid), mode="bicubic", align_corners=False)
+    if antialias:
+        pp = torch.nn.functional.interpolate(pp, size=(grid, grid), mode="bicubic", align_corners=False, antialias=True)
+    else:
+        pp = torch.nn.functional.interpolate(pp, size=(grid, grid), mode="bicubic", align_corners=False)
     pp = pp.permute(0, 2, 3, 1).reshape(grid * grid, d)
     return torch.cat([cls, pp], dim=0)
+
+
+def pos_with_registers(pos: torch.Tensor, registers: int) -> torch.Tensor:
+    """[1 + P, d] -> [1 + R + P, d] in token-row order: R zero rows after the CLS row (registers carry no position term)."""
+    if registers <= 0:
+        return pos
+    return torch.cat([pos[:1], pos.new_zeros(registers, pos.shape[1]), pos[1:]], dim=0)
 
 
 def pack_hf_state_dict(sd: Dict[str, torch.Tensor], spec: ViTSpec) -> dict:
@@ -185,7 +217,7 @@ def pack_hf_state_dict(sd: Dict[str, torch.Tensor], spec: ViTSpec) -> dict:
         names = dict(q="self_attn.q_proj", k="self_attn.k_proj", v="self_attn.v_proj", o="self_attn.out_proj",
                      ln1="layer_norm1", ln2="layer_norm2", fc1="mlp.fc1", fc2="mlp.fc2")
     elif spec.family == "dinov2":
-        s = _strip(sd, ["dinov2."])
+        s = _strip(sd, ["dinov2_with_registers.", "dinov2."])
         w = {
             "patch_w": s["embeddings.patch_embeddings.projection.weight"].reshape(d, -1),
             "patch_b": s["embeddings.patch_embeddings.projection.bias"],
@@ -203,7 +235,9 @@ def pack_hf_state_dict(sd: Dict[str, torch.Tensor], spec: ViTSpec) -> dict:
     # The checkpoint's own grid stays in the packed weights: a later change of resolution (weights_at_resolution) must resize from
     # IT, once, like HF's interpolate_pos_encoding does (37 x 37 -> target), not from the already-resized table (37 -> 16 -> 24).
     w["pos_native"] = w["pos"]
-    w["pos"] = interpolate_pos(w["pos"], spec.has_cls, spec.grid)
+    w["pos"] = pos_with_registers(interpolate_pos(w["pos"], spec.has_cls, spec.grid, antialias=spec.registers > 0), spec.registers)
+    if spec.registers:
+        w["reg"] = s["embeddings.register_tokens"].reshape(spec.registers, d)
     layers = []
     for i in range(spec.layers):
         L = {
@@ -261,7 +295,18 @@ def synthetic_weights(spec: ViTSpec, seed: int = 1, n_layers: Optional[int] = No
             "ls2": rn(d, std=0.02, mean=0.1) if spec.layerscale else None,
         })
     w["layers"] = layers
+    if spec.registers:                                           # drawn after everything else: every spec without registers keeps its stream
+        w["reg"] = rn(spec.registers, d)
+        w["pos"] = w["pos"].clone()
+        w["pos"][1:1 + spec.registers] = 0.0                     # registers carry no position term
     return w
+
+
+def prefix_table(spec: ViTSpec, w: dict) -> Optional[torch.Tensor]:
+    """What the engines hand the library as `cls`: [d] for a plain CLS tower, [1 + R, d] = the class token, then the registers."""
+    if not spec.registers:
+        return w.get("cls")
+    return torch.cat([w["cls"].reshape(1, spec.d).float(), w["reg"].reshape(spec.registers, spec.d).float()], dim=0)
 
 
 def flatten(w: dict) -> Dict[str, torch.Tensor]:
@@ -295,8 +340,10 @@ def weights_at_resolution(spec: ViTSpec, w: dict, image_size: int):
     src = w.get("pos_native")
     if src is None:
         src = w["pos"]
+        if spec.registers:                                   # the packed table: pos_native is the checkpoint's form, without register rows
+            src = torch.cat([src[:1], src[1 + spec.registers:]], dim=0)
     w2["pos_native"] = src                                   # every later resize starts from the same table
-    w2["pos"] = interpolate_pos(src, spec.has_cls, spec2.grid)
+    w2["pos"] = pos_with_registers(interpolate_pos(src, spec.has_cls, spec2.grid, antialias=spec.registers > 0), spec.registers)
     return spec2, w2
 
 
@@ -366,7 +413,7 @@ def hostile_weights(spec: ViTSpec, seed: int = 1, n_layers: Optional[int] = None
                     L["bqkv"][base + hd * dh: base + (hd + 1) * dh] *= sharp
     tok = None
     if profile in ("const", "all"):
-        tok = min(int(const_token) + (1 if spec.has_cls else 0), spec.tokens - 1)
+        tok = min(int(const_token) + spec.prefix, spec.tokens - 1)
         w["pos"] = w["pos"].clone()
         w["pos"][tok] += const_value
     w["hostile"] = {"profile": profile, "channels": ch.tolist() if plant else [], "factors": fac.tolist() if plant else [], "const_token": tok,
