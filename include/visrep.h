@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define VISREP_VERSION 640   /* 640: DINOv2-with-registers towers - visrep_vit_config grows a trailing `registers` (struct change), visrep_vit_weights::cls may be a [1 + registers, d] table, visrep_mhsa_prefix_fwd / visrep_mhsa_prefix_supported / visrep_prefix_rows, route id 13.  630: SwiGLU-FFN towers (DINOv2-giant) - VISREP_ACT_SWIGLU = 4 in visrep_vit_config::act (w1 / b1 / s1 then have 2 * mlp rows), VISREP_EPI_GATED, visrep_gemm_bf16_gated, visrep_swiglu, visrep_swiglu_f32, visrep_set_fuse_gate, visrep_debug_gated_refusal (new exports / newly accepted argument values; no struct layout change).  620: head widths other than 64 in the bf16 tower - visrep_vit_config grows head_dim / head_pad (struct change), visrep_mhsa_fwd takes head_dim 64 | 96 | 128, visrep_attention_fwd head_dim 96, route id 12; visrep_im2col and visrep_vit_forward_cpu no longer refuse an image side that is not a multiple of the patch - they floor the division as Conv2d does (newly accepted argument values).  610: visrep_cscore_transfer_packed2 / visrep_cscore_transfer2_cpu, the key-point transfer on two per-encoder banks (new exports only).  600 = round 6: reserved CUs, GEMM tile-walk knob, gemm variants 6-8, visrep_masked_nn_min_f32, window < 0 in the C-score transfers (new exports / newly accepted argument values only).  500 = round 5: device CU count, routing counters, MFMA probe, A-score reference arithmetic, host twins (new exports only).  410 = round 4: split-route `products`, stream-keyed scratch, per-thread knobs (changed signatures); 410: q_prescaled = 2, row-mapped GEMM, image-aligned / wide-head attention, conv + GroupNorm partials */
+#define VISREP_VERSION 650   /* 650: InternViT towers - visrep_vit_config grows trailing `norm` / `qk_norm`, visrep_vit_layer trailing `qn_g` / `kn_g` (struct changes), visrep_rmsnorm / visrep_rmsnorm_stats / visrep_qk_rmsnorm (+ _f32 / _cpu forms), visrep_gemm_bf16_resid_rms_stats, route ids 14 .. 18.  640: DINOv2-with-registers towers - visrep_vit_config grows a trailing `registers` (struct change), visrep_vit_weights::cls may be a [1 + registers, d] table, visrep_mhsa_prefix_fwd / visrep_mhsa_prefix_supported / visrep_prefix_rows, route id 13.  630: SwiGLU-FFN towers (DINOv2-giant) - VISREP_ACT_SWIGLU = 4 in visrep_vit_config::act (w1 / b1 / s1 then have 2 * mlp rows), VISREP_EPI_GATED, visrep_gemm_bf16_gated, visrep_swiglu, visrep_swiglu_f32, visrep_set_fuse_gate, visrep_debug_gated_refusal (new exports / newly accepted argument values; no struct layout change).  620: head widths other than 64 in the bf16 tower - visrep_vit_config grows head_dim / head_pad (struct change), visrep_mhsa_fwd takes head_dim 64 | 96 | 128, visrep_attention_fwd head_dim 96, route id 12; visrep_im2col and visrep_vit_forward_cpu no longer refuse an image side that is not a multiple of the patch - they floor the division as Conv2d does (newly accepted argument values).  610: visrep_cscore_transfer_packed2 / visrep_cscore_transfer2_cpu, the key-point transfer on two per-encoder banks (new exports only).  600 = round 6: reserved CUs, GEMM tile-walk knob, gemm variants 6-8, visrep_masked_nn_min_f32, window < 0 in the C-score transfers (new exports / newly accepted argument values only).  500 = round 5: device CU count, routing counters, MFMA probe, A-score reference arithmetic, host twins (new exports only).  410 = round 4: split-route `products`, stream-keyed scratch, per-thread knobs (changed signatures); 410: q_prescaled = 2, row-mapped GEMM, image-aligned / wide-head attention, conv + GroupNorm partials */
 
 enum { VISREP_BF16 = 0, VISREP_F32 = 1 };
 enum { VISREP_OK = 0, VISREP_ERR_ARG = -1, VISREP_ERR_SHAPE = -2, VISREP_ERR_LAUNCH = -3 };
@@ -91,7 +91,12 @@ enum {
     VISREP_ROUTE_CONV_C8 = 11,       /* conv3x3_c8: the VAE's first convolution straight from 8-channel pixel tokens (no im2col) */
     VISREP_ROUTE_ATTN_96 = 12,       /* attn_fwd96 (head width 96: true widths 65 .. 96 zero-padded) */
     VISREP_ROUTE_ATTN_PREFIX = 13,   /* attn_fwd_prefix (image-aligned towers with CLS + register tokens) */
-    VISREP_ROUTE_COUNT = 14
+    VISREP_ROUTE_STATS_EPILOGUE = 14, /* row statistics of a residual GEMM from its epilogue's partial sums (ln_stats_finalize_rows / rms_stats_finalize_rows) */
+    VISREP_ROUTE_STATS_REDUCE = 15,  /* ... written by the split-K reduction itself (N == 1024) */
+    VISREP_ROUTE_STATS_ROWS = 16,    /* the read-only statistics pass over bf16 rows (visrep_layernorm_stats / visrep_rmsnorm_stats, called or fallen back to) */
+    VISREP_ROUTE_RMS = 17,           /* any of the above, or a visrep_rmsnorm pass, in its RMS form */
+    VISREP_ROUTE_QK_NORM = 18,       /* qk_rmsnorm_rows (visrep_qk_rmsnorm) */
+    VISREP_ROUTE_COUNT = 19
 };
 int visrep_debug_routes(long* out, int reset);
 /* Matrix-pipe ceiling of THIS device under THIS process' conditions: `iters` bursts of 32 dependent-free v_mfma_f32_16x16x32_bf16 per wave,
@@ -293,13 +298,23 @@ typedef struct {
      * grid^2 + has_cls + registers; token rows of an image: CLS, the registers, the patches.  0 = every tower before 640, unchanged.
      * With q_prescaled == 2 and 64 n patches such a tower (prefix = 1 + registers <= 8) runs visrep_mhsa_prefix_fwd. */
     int registers;
+    /* norm: the two pre-block norms - 0 = nn.LayerNorm (every tower before 650), 1 = RMSNorm (HF InternVLVisionRMSNorm: x * rsqrt(mean(x^2) + eps)
+     * * ln*_g, no bias; ln*_b are ignored; d <= 4096; pre_ln is refused).  The folded route is the same GEMM epilogue fed with statistics
+     * (rstd, 0).  qk_norm != 0: an RMSNorm over the WHOLE width (all heads, before the head split; eps VISREP_QK_NORM_EPS) is applied to the
+     * Q and to the K projection's output with the layer's qn_g / kn_g (visrep_qk_rmsnorm between the Q|K GEMM and the attention kernel).  With
+     * q_prescaled != 0 the packer folds head_dim^-0.5 * log2(e) into qn_g, NOT into the Q rows of wqkv / bqkv.  Both 0 = unchanged launches. */
+    int norm, qk_norm;
 } visrep_vit_config;
+#define VISREP_QK_NORM_EPS 1e-6f   /* HF InternVLVisionAttention: q_norm / k_norm are built with the RMSNorm class default, not layer_norm_eps */
 typedef struct {           /* device pointers; matrices bf16 [out,in], vectors fp32; ls1/ls2 NULL when no LayerScale */
     const float *ln1_g, *ln1_b; const void* wqkv; const float* bqkv; const void* wo; const float* bo; const float* ls1;
     const float *ln2_g, *ln2_b; const void* w1; const float* b1; const void* w2; const float* b2; const float* ls2;
     /* LayerNorm folded into the consuming GEMMs (both non-NULL to enable; ln*_g / ln*_b are then unused): wqkv = gamma1 o Wqkv and
      * bqkv = Wqkv beta1 + b (likewise w1 / b1 with LN2), sqkv[n] = sum_k wqkv[n, k] over the bf16-rounded rows [3d], s1 [mlp]. */
     const float *sqkv, *s1;
+    /* qk_norm towers: the RMSNorm weights behind q_proj / k_proj.  bf16 tower: [heads * head_pad], zero in the padded columns; fp32 and host
+     * towers: [d].  NULL otherwise. */
+    const float *qn_g, *kn_g;
 } visrep_vit_layer;
 typedef struct {
     const void* patch_w;   /* bf16 [d, kpad], zero padded past 3*p*p */
@@ -313,6 +328,29 @@ size_t visrep_vit_workspace_bytes(const visrep_vit_config* cfg, int B);
 /* hidden: [B, tokens, d] bf16 — receives hidden_states[n_layers] (the residual stream lives in it). */
 int visrep_vit_forward(const visrep_vit_config* cfg, const visrep_vit_weights* w, const void* pixels, int pixel_dtype, void* hidden,
                        int B, int n_layers, void* workspace, void* stream);
+
+/* ---- RMSNorm (HF InternVLVisionRMSNorm; rowops.hip).  One wave per row, fp32 sum of squares, d % 8 == 0, d <= 4096, ldx / ldy % 8 == 0,
+ * 16-byte aligned pointers (gamma included); refused before any launch otherwise.
+ * visrep_rmsnorm: y = x * rsqrt(mean(x^2) + eps) * gamma, rounded once to bf16; y may alias x.
+ * visrep_rmsnorm_stats: rt[row] = (rsqrt(mean(x^2) + eps), 0) - the (rstd, -mean * rstd) pair of visrep_layernorm_stats with an exact zero
+ * second term, so that visrep_gemm_bf16_ln computes Linear(RMSNorm(x)) from W = gamma o W_orig unchanged (ln_s must be finite).
+ * visrep_gemm_bf16_resid_rms_stats: visrep_gemm_bf16_resid_stats leaving that pair for its output rows (N <= 4096).
+ * visrep_qk_rmsnorm: in place on qk [rows, ldqk] = the Q|K GEMM's output, Q in columns [0, width), K in [width, 2 width), width = heads *
+ * head_pad <= 4096, % 8 == 0; ldqk % 8 == 0, >= 2 width.  Each half of each row: x * rsqrt(sum(x^2) / d_true + eps) * g[c] in fp32, one
+ * rounding to bf16; g = qn_g for Q, kn_g for K ([width] fp32; zero in padded columns, which therefore stay zero).  d_true = heads * head_dim
+ * (0 < d_true <= width): zero-padded columns add nothing to the sum and must not count in the mean.  Nothing outside the 2 width columns
+ * of the `rows` rows is written.  Memory-bound: reads and writes 4 * rows * width bytes. */
+int visrep_rmsnorm(const void* x, int ldx, const float* gamma, void* y, int ldy, int rows, int d, float eps, void* stream);
+int visrep_rmsnorm_stats(const void* x, int ldx, void* rt, int rows, int d, float eps, void* stream);
+int visrep_qk_rmsnorm(void* qk, int ldqk, int width, int d_true, const float* qn_g, const float* kn_g, int rows, float eps, void* stream);
+int visrep_gemm_bf16_resid_rms_stats(const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc, int M, int N, int K,
+                                     const void* resid, const float* ls, void* rt, void* partial, float eps, void* stream);
+/* fp32 forms (device pointers, any d / width that is a multiple of 4) and host twins (HOST pointers, fp32, double-precision sums) */
+int visrep_rmsnorm_f32(const float* x, int ldx, const float* gamma, float* y, int ldy, int rows, int d, float eps, void* stream);
+int visrep_qk_rmsnorm_f32(float* qk, int ldqk, int width, int d_true, const float* qn_g, const float* kn_g, int rows, float eps, void* stream);
+int visrep_rmsnorm_cpu(const float* x, int ldx, const float* gamma, float* y, int ldy, long rows, int d, float eps, int threads);
+int visrep_rmsnorm_stats_cpu(const float* x, int ldx, float* rt, long rows, int d, float eps, int threads);
+int visrep_qk_rmsnorm_cpu(float* qk, int ldqk, int width, int d_true, const float* qn_g, const float* kn_g, long rows, float eps, int threads);
 
 /* ---- reference-precision (fp32) tower path.  The reference builds the C-score CLIP / OpenCLIP / DINOv2 towers with no dtype cast and
  * fp32 pixels (C_score/extract_feature.py:36-45,49-50,80-87): every tensor and accumulation here is fp32 (v_mfma_f32_32x32x2_f32 = an
@@ -351,7 +389,8 @@ int visrep_split_bf16_planes(const float* x, int ldx, long rows, int K, int npla
  * with libm expf / erff / tanhf. */
 int visrep_gemm_f32_split(const void* a_planes, const void* w_planes, int M, int N, int K, int products, const float* bias, int act,
                           const float* resid, const float* ls, float* C, int ldc, void* out_planes, void* stream);
-/* 1 when visrep_vit_forward_f32_split takes this tower (d, mlp % 256 == 0, head width 64) */
+/* 1 when visrep_vit_forward_f32_split takes this tower (d, mlp % 256 == 0, head width 64, norm == 0 and qk_norm == 0: RMSNorm / QK-norm towers
+ * take the exact-fp32 route) */
 int visrep_vit_f32_split_supported(const visrep_vit_config* cfg);
 /* visrep_vit_forward_f32 with the projections and the attention as split-bf16 products.  w: the fp32 weights (vectors, patch matrix); wsplit:
  * same struct whose wqkv / wo / w1 / w2 point to the planes [N, npl K] of the fp32 matrices (other fields ignored); products as above.

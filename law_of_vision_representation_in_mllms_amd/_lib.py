@@ -11,22 +11,25 @@ import threading
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VISREP_LIB") or os.path.join(_PKG, "libvisrep_hip.so")   # VISREP_LIB: diagnostic builds only
 
-ABI_VERSION = 640                 # include/visrep.h VISREP_VERSION this binding was written against (checked at load)
+ABI_VERSION = 650                 # include/visrep.h VISREP_VERSION this binding was written against (checked at load)
 BF16, F32 = 0, 1
 EPI_BIAS, EPI_ACT, EPI_RESID, EPI_VT, EPI_PATCH, EPI_F32 = range(6)
 EPI_GATED = 7
+NORM = {"layernorm": 0, "rmsnorm": 1}
+QK_NORM_EPS = 1e-6                # include/visrep.h VISREP_QK_NORM_EPS
 ACT = {"none": 0, "quick_gelu": 1, "gelu": 2, "gelu_erf": 2, "gelu_tanh": 3, "gelu_pytorch_tanh": 3, "swiglu": 4}
 
 
 class VitConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("image_size", "patch", "d", "heads", "mlp", "layers", "tokens", "has_cls", "pre_ln",
                                        "act", "kpad")] + [("eps", C.c_float), ("q_prescaled", C.c_int), ("head_dim", C.c_int),
-                                                                    ("head_pad", C.c_int), ("registers", C.c_int)]
+                                                                    ("head_pad", C.c_int), ("registers", C.c_int),
+                                                                    ("norm", C.c_int), ("qk_norm", C.c_int)]
 
 
 class VitLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ln1_g", "ln1_b", "wqkv", "bqkv", "wo", "bo", "ls1", "ln2_g", "ln2_b", "w1", "b1",
-                                          "w2", "b2", "ls2", "sqkv", "s1")]
+                                          "w2", "b2", "ls2", "sqkv", "s1", "qn_g", "kn_g")]
 
 
 class VitWeights(C.Structure):
@@ -64,6 +67,15 @@ SIGNATURES = {
     "visrep_gemm_bf16_ln": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "visrep_gemm_bf16_rows": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "visrep_gemm_bf16_resid_stats": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp]),
+    "visrep_gemm_bf16_resid_rms_stats": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp]),
+    "visrep_rmsnorm": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "visrep_rmsnorm_stats": (_i, [_vp, _i, _vp, _i, _i, _f, _vp]),
+    "visrep_qk_rmsnorm": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _f, _vp]),
+    "visrep_rmsnorm_f32": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "visrep_qk_rmsnorm_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _f, _vp]),
+    "visrep_rmsnorm_cpu": (_i, [_vp, _i, _vp, _vp, _i, _l, _i, _f, _i]),
+    "visrep_rmsnorm_stats_cpu": (_i, [_vp, _i, _vp, _l, _i, _f, _i]),
+    "visrep_qk_rmsnorm_cpu": (_i, [_vp, _i, _i, _i, _vp, _vp, _l, _f, _i]),
     "visrep_gemm_bf16_gated": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "visrep_swiglu": (_i, [_vp, _i, _vp, _i, _l, _i, _vp]),
     "visrep_swiglu_f32": (_i, [_vp, _i, _vp, _i, _l, _i, _vp]),
@@ -183,7 +195,8 @@ def load(build_if_missing: bool = True):
         return lib
 
 
-ROUTES = ("gemm_256", "gemm_128", "gemm_tail", "splitk", "conv_256", "conv_128", "conv_128_gn", "attn", "attn_wide", "attn_cls", "conv_halo", "conv_c8", "attn_96", "attn_prefix")
+ROUTES = ("gemm_256", "gemm_128", "gemm_tail", "splitk", "conv_256", "conv_128", "conv_128_gn", "attn", "attn_wide", "attn_cls", "conv_halo", "conv_c8", "attn_96", "attn_prefix",
+          "stats_epilogue", "stats_reduce", "stats_rows", "rms", "qk_norm")
 
 
 def xcd_balance() -> dict:

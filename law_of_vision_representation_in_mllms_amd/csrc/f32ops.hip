@@ -840,6 +840,7 @@ int launch_gemm_split(const bf16_t* Ap, const bf16_t* Wp, int M, int N, int K, i
 }
 
 bool split_route_supported(const visrep_vit_config* c) {
+    if (c->norm != 0 || c->qk_norm != 0) return false;        // RMSNorm / QK-norm towers (InternViT): the exact-fp32 route
     return c->d % 256 == 0 && c->mlp % 256 == 0 && c->d % 64 == 0 && c->mlp % 64 == 0 && (c->d / c->heads) == 64;
 }
 
@@ -958,6 +959,12 @@ extern "C" int visrep_vit_forward_f32(const visrep_vit_config* c, const visrep_v
     const int grid = c->image_size / c->patch;
     if (c->registers < 0 || (c->registers > 0 && !c->has_cls)) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32: register tokens need a CLS token");
     if (grid * grid + (c->has_cls ? 1 : 0) + c->registers != c->tokens) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32: tokens != grid^2 + cls + registers");
+    if (c->norm != 0 && c->norm != 1) return visrep_set_error(VISREP_ERR_ARG, "vit_forward_f32: norm must be 0 (LayerNorm) or 1 (RMSNorm)");
+    const bool rms = c->norm == 1;
+    if (rms && c->pre_ln) return visrep_set_error(VISREP_ERR_ARG, "vit_forward_f32: pre_ln with RMSNorm blocks is not supported");
+    if (c->qk_norm)
+        for (int l = 0; l < n_layers; ++l)
+            if (!w->layers[l].qn_g || !w->layers[l].kn_g) return visrep_set_error(VISREP_ERR_ARG, "vit_forward_f32: a qk_norm tower needs qn_g and kn_g in every layer");
     hipStream_t s = (hipStream_t)stream;
     const WsF32 L = layout_f32(c, B);
     char* base = (char*)workspace;
@@ -983,11 +990,12 @@ extern "C" int visrep_vit_forward_f32(const visrep_vit_config* c, const visrep_v
     const float scale = 1.0f / sqrtf((float)dh);
     for (int l = 0; l < n_layers; ++l) {
         const visrep_vit_layer& W = w->layers[l];
-        VR_TRY(visrep_layernorm_f32(x, d, W.ln1_g, W.ln1_b, h, d, M, d, c->eps, stream));
+        VR_TRY(rms ? visrep_rmsnorm_f32(x, d, W.ln1_g, h, d, M, d, c->eps, stream) : visrep_layernorm_f32(x, d, W.ln1_g, W.ln1_b, h, d, M, d, c->eps, stream));
         GemmF32Args a{};
         a.alpha = 1.f; a.nb2 = 1;
         a.A = h; a.lda = d; a.K = d; a.M = M; a.W = (const float*)W.wqkv; a.ldw = d; a.N = 3 * d; a.C = qkv; a.ldc = 3 * d; a.bias = W.bqkv; a.epi = EPI_BIAS;
         VR_TRY(launch_gemm_f32(a, 1, s));
+        if (c->qk_norm) VR_TRY(visrep_qk_rmsnorm_f32(qkv, 3 * d, d, d, W.qn_g, W.kn_g, M, VISREP_QK_NORM_EPS, stream));
         if (dh == 64 && !(t_visrep_f32_attention_dbg & 1)) {
             // fused flash-style fp32 attention: scores stay in registers (attn_f32_kernel)
             AttnF32Args at{qkv, qkv + d, qkv + 2 * d, h, B, T, H, 3 * d, d, scale * 1.4426950408889634f};
@@ -1009,7 +1017,7 @@ extern "C" int visrep_vit_forward_f32(const visrep_vit_config* c, const visrep_v
         // out projection + LayerScale + residual (in place on x)
         a.A = h; a.W = (const float*)W.wo; a.N = d; a.C = x; a.ldc = d; a.bias = W.bo; a.epi = EPI_RESID; a.resid = x; a.ls = W.ls1;
         VR_TRY(launch_gemm_f32(a, 1, s));
-        VR_TRY(visrep_layernorm_f32(x, d, W.ln2_g, W.ln2_b, h, d, M, d, c->eps, stream));
+        VR_TRY(rms ? visrep_rmsnorm_f32(x, d, W.ln2_g, h, d, M, d, c->eps, stream) : visrep_layernorm_f32(x, d, W.ln2_g, W.ln2_b, h, d, M, d, c->eps, stream));
         GemmF32Args f{};
         f.alpha = 1.f; f.nb2 = 1;
         f.A = h; f.lda = d; f.K = d; f.M = M; f.W = (const float*)W.w1; f.ldw = d; f.N = c->mlp; f.C = mlp; f.ldc = c->mlp; f.bias = W.b1; f.epi = EPI_ACT; f.act = c->act;
@@ -1042,7 +1050,7 @@ extern "C" int visrep_vit_forward_f32_split(const visrep_vit_config* c, const vi
     const int npl = visrep_split_planes(products);
     if (B <= 0) return 0;
     if (n_layers < 0 || n_layers > c->layers) return visrep_set_error(VISREP_ERR_ARG, "vit_forward_f32_split: n_layers out of range");
-    if (!split_route_supported(c)) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32_split: d and mlp must be multiples of 256, head width 64");
+    if (!split_route_supported(c)) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32_split: d and mlp must be multiples of 256, head width 64, LayerNorm blocks without QK norm");
     const int grid = c->image_size / c->patch;
     if (c->registers < 0 || (c->registers > 0 && !c->has_cls)) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32_split: register tokens need a CLS token");
     if (grid * grid + (c->has_cls ? 1 : 0) + c->registers != c->tokens) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_f32_split: tokens != grid^2 + cls + registers");

@@ -235,6 +235,38 @@ __global__ __launch_bounds__(256) void splitk_reduce(const float* __restrict__ p
         }
     }
 }
+// The residual reduction of a RMSNorm tower at N == 1024 (GemmArgs::stat_rms; splitk_reduce_emits_stats): out = resid + ls * (sum_s part[s] + bias),
+// and - this block IS row m - stat_rt[m] = (rsqrt(mean(out^2) + eps), 0) over the bf16-ROUNDED outputs, rms_stats_finalize_rows' formula.
+__global__ __launch_bounds__(256) void splitk_reduce_rms(const float* __restrict__ part, int S, const GemmArgs p) {
+    const int m = blockIdx.x, n = threadIdx.x * 4;               // N == 1024 = 4 * blockDim, grid = M
+    const size_t plane = (size_t)p.M * 1024;
+    float4 acc = *reinterpret_cast<const float4*>(part + (size_t)m * 1024 + n);
+    for (int s = 1; s < S; ++s) {
+        const float4 v = *reinterpret_cast<const float4*>(part + s * plane + (size_t)m * 1024 + n);
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    if (p.bias) {
+        const float4 b = *reinterpret_cast<const float4*>(p.bias + n);
+        acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
+    }
+    if (p.ls) {
+        const float4 l = *reinterpret_cast<const float4*>(p.ls + n);
+        acc.x *= l.x; acc.y *= l.y; acc.z *= l.z; acc.w *= l.w;
+    }
+    const u32x2 r = *reinterpret_cast<const u32x2*>(p.resid + (size_t)m * p.ldc + n);
+    acc.x += bf_lo(r[0]); acc.y += bf_hi(r[0]); acc.z += bf_lo(r[1]); acc.w += bf_hi(r[1]);
+    u32x2 o = {pack_bf16(acc.x, acc.y), pack_bf16(acc.z, acc.w)};
+    *reinterpret_cast<u32x2*>(p.C + (size_t)m * p.ldc + n) = o;
+    __shared__ float red[4];
+    const float r0 = bf_lo(o[0]), r1 = bf_hi(o[0]), r2 = bf_lo(o[1]), r3 = bf_hi(o[1]);
+    const float s2 = wave_sum(__builtin_fmaf(r0, r0, __builtin_fmaf(r1, r1, __builtin_fmaf(r2, r2, r3 * r3))));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s2;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float t2 = (red[0] + red[1]) + (red[2] + red[3]);
+        p.stat_rt[m] = float2{1.0f / sqrtf(t2 * (1.0f / 1024.0f) + p.stat_eps), 0.f};
+    }
+}
 bool splitk_reduce_emits_stats(const GemmArgs& a) { return a.stat_rt && a.epi == EPI_RESID && a.N == 1024; }
 
 }  // namespace
@@ -429,7 +461,10 @@ int try_split_k(const GemmArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(splitk_reduce_vt, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, (const float*)scratch, S, a);
     } else {
         const long nthreads = (long)a.M * (a.N / 4);
-        hipLaunchKernelGGL(splitk_reduce, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, (const float*)scratch, S, a);
+        if (a.stat_rms && splitk_reduce_emits_stats(a))          // EPI_RESID, N == 1024 (a folded norm on the input side is refused by the dispatcher): one block per row
+            hipLaunchKernelGGL(splitk_reduce_rms, dim3((unsigned)a.M), dim3(256), 0, s, (const float*)scratch, S, a);
+        else
+            hipLaunchKernelGGL(splitk_reduce, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, s, (const float*)scratch, S, a);
     }
     return hipGetLastError() == hipSuccess ? 1 : visrep_set_error(VISREP_ERR_LAUNCH, "gemm: split-K reduce launch failed");
 }
@@ -443,6 +478,10 @@ bool v2_emits_stats(const GemmArgs& a, int variant) {
 // rows [0, a.M) of a finished residual GEMM -> a.stat_rt: from the epilogue's partial sums, else by reading the rows back
 int finish_stats(const GemmArgs& a, bool from_partials, hipStream_t s) {
     if (!a.stat_rt) return 0;
+    if (a.stat_rms) {
+        if (from_partials) return visrep_rms_stats_finalize(a.stat_partial, a.N / 64, a.stat_rt, a.M, a.N, a.stat_eps, s);
+        return visrep_rmsnorm_stats(a.C, a.ldc, a.stat_rt, a.M, a.N, a.stat_eps, s);
+    }
     if (from_partials) return visrep_ln_stats_finalize(a.stat_partial, a.N / 64, a.stat_rt, a.M, a.N, a.stat_eps, s);
     return visrep_layernorm_stats(a.C, a.ldc, a.stat_rt, a.M, a.N, a.stat_eps, s);
 }
@@ -457,7 +496,11 @@ int run_one(const GemmArgs& a, hipStream_t s, int variant) {
 int run_split_k(const GemmArgs& a, hipStream_t s) {              // 1 = handled, 0 = not eligible, < 0 = error
     const int sk = try_split_k(a, s);
     if (sk <= 0) return sk;
-    if (splitk_reduce_emits_stats(a)) return 1;                  // the reduction wrote stat_rt for its rows
+    if (splitk_reduce_emits_stats(a)) {                          // the reduction wrote stat_rt for its rows
+        visrep_count_route(VISREP_ROUTE_STATS_REDUCE);
+        if (a.stat_rms) visrep_count_route(VISREP_ROUTE_RMS);
+        return 1;
+    }
     const int rc = finish_stats(a, false, s);
     return rc ? rc : 1;
 }
@@ -486,6 +529,7 @@ int visrep_gemm_dispatch(const GemmArgs& a, hipStream_t s) {
         if (a.resid || a.ls) return visrep_set_error(VISREP_ERR_ARG, "gemm: the gated epilogue takes no residual / LayerScale");
     }
     if (a.stat_rt && a.epi != EPI_RESID) return visrep_set_error(VISREP_ERR_ARG, "gemm: row statistics are an EPI_RESID feature");
+    if (a.stat_rt && a.stat_rms && (a.ln_rt || a.ln_s)) return visrep_set_error(VISREP_ERR_ARG, "gemm: RMS row statistics do not combine with a folded norm on the input side");
     if (a.a_period > 0 && (a.conv || a.epi == EPI_RESID || a.epi == EPI_PATCH || a.a_stride < a.a_period || a.a_first < 0))
         return visrep_set_error(VISREP_ERR_ARG, "gemm: the A row map serves plain BIAS / ACT / VT / F32 epilogues only");
     if (a.gn_partial && (!a.conv || (a.epi != EPI_BIAS && a.epi != EPI_RESID) || (a.gn_cpg != 4 && a.gn_cpg != 8 && a.gn_cpg != 16) || a.gn_hw <= 0 ||

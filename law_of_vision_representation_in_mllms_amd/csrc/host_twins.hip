@@ -95,6 +95,24 @@ void layernorm_rows_cpu(const float* x, const float* g, const float* b, float* y
     });
 }
 
+// RMSNorm of `halves` consecutive blocks of d floats per row (HF InternVLVisionRMSNorm): y = x * rsqrt(sum(x^2) / d_true + eps) * g, the sum in
+// double and in column order (zero-padded columns add exactly nothing).  halves = 1: the block norm; 2: Q | K with gains g / g2.  y may alias x.
+void rmsnorm_rows_cpu(const float* x, int ldx, const float* g, const float* g2, float* y, int ldy, long rows, int d, int halves, int d_true, float eps,
+                      int threads) {
+    parallel_for((rows + 63) / 64, threads, [&](long blk) {
+        for (long r = blk * 64; r < std::min<long>(rows, blk * 64 + 64); ++r)
+            for (int hf = 0; hf < halves; ++hf) {
+                const float* xr = x + (size_t)r * ldx + (size_t)hf * d;
+                float* yr = y + (size_t)r * ldy + (size_t)hf * d;
+                const float* gg = hf ? g2 : g;
+                double ss = 0.0;
+                for (int i = 0; i < d; ++i) ss += (double)xr[i] * xr[i];
+                const float rstd = (float)(1.0 / sqrt(ss / d_true + (double)eps));
+                for (int i = 0; i < d; ++i) yr[i] = xr[i] * rstd * gg[i];
+            }
+    });
+}
+
 float act_cpu(float x, int act) {
     switch (act) {
         case VISREP_ACT_QUICK_GELU: return x * (1.0f / (1.0f + expf(-1.702f * x)));                     // HF QuickGELUActivation
@@ -105,6 +123,36 @@ float act_cpu(float x, int act) {
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------ RMSNorm twins
+extern "C" int visrep_rmsnorm_cpu(const float* x, int ldx, const float* gamma, float* y, int ldy, long rows, int d, float eps, int threads) {
+    if (!x || !gamma || !y) return visrep_set_error(VISREP_ERR_ARG, "rmsnorm_cpu: null pointer");
+    if (d <= 0 || ldx < d || ldy < d) return visrep_set_error(VISREP_ERR_SHAPE, "rmsnorm_cpu: ldx, ldy >= d > 0 required");
+    if (rows > 0) rmsnorm_rows_cpu(x, ldx, gamma, gamma, y, ldy, rows, d, 1, d, eps, threads);
+    return 0;
+}
+
+extern "C" int visrep_rmsnorm_stats_cpu(const float* x, int ldx, float* rt, long rows, int d, float eps, int threads) {
+    if (!x || !rt) return visrep_set_error(VISREP_ERR_ARG, "rmsnorm_stats_cpu: null pointer");
+    if (d <= 0 || ldx < d) return visrep_set_error(VISREP_ERR_SHAPE, "rmsnorm_stats_cpu: ldx >= d > 0 required");
+    parallel_for((rows + 63) / 64, threads, [&](long blk) {
+        for (long r = blk * 64; r < std::min<long>(rows, blk * 64 + 64); ++r) {
+            double ss = 0.0;
+            for (int i = 0; i < d; ++i) ss += (double)x[(size_t)r * ldx + i] * x[(size_t)r * ldx + i];
+            rt[2 * r] = (float)(1.0 / sqrt(ss / d + (double)eps));
+            rt[2 * r + 1] = 0.f;
+        }
+    });
+    return 0;
+}
+
+extern "C" int visrep_qk_rmsnorm_cpu(float* qk, int ldqk, int width, int d_true, const float* qn_g, const float* kn_g, long rows, float eps, int threads) {
+    if (!qk || !qn_g || !kn_g) return visrep_set_error(VISREP_ERR_ARG, "qk_rmsnorm_cpu: null pointer");
+    if (width <= 0 || ldqk < 2 * width || d_true <= 0 || d_true > width)
+        return visrep_set_error(VISREP_ERR_SHAPE, "qk_rmsnorm_cpu: ldqk >= 2 * width, 0 < d_true <= width required");
+    if (rows > 0) rmsnorm_rows_cpu(qk, ldqk, qn_g, kn_g, qk, ldqk, rows, width, 2, d_true, eps, threads);
+    return 0;
+}
 
 // ------------------------------------------------------------------------------------------------ ViT tower
 extern "C" int visrep_vit_forward_cpu(const visrep_vit_config* c, const visrep_vit_weights* w, const float* pixels, float* hidden, int B, int n_layers,
@@ -119,6 +167,12 @@ extern "C" int visrep_vit_forward_cpu(const visrep_vit_config* c, const visrep_v
     if (grid <= 0 || P + (c->has_cls ? 1 : 0) + c->registers != T) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_cpu: tokens != grid^2 + cls + registers");
     const int kp = 3 * p * p, kpad = c->kpad > 0 ? c->kpad : kp;       // patch_w rows are kpad floats wide (zero padded past 3 p p)
     if (kpad < kp) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward_cpu: kpad < 3 * patch^2");
+    if (c->norm != 0 && c->norm != 1) return visrep_set_error(VISREP_ERR_ARG, "vit_forward_cpu: norm must be 0 (LayerNorm) or 1 (RMSNorm)");
+    const bool rms = c->norm == 1;
+    if (rms && c->pre_ln) return visrep_set_error(VISREP_ERR_ARG, "vit_forward_cpu: pre_ln with RMSNorm blocks is not supported");
+    if (c->qk_norm)
+        for (int l = 0; l < n_layers; ++l)
+            if (!w->layers[l].qn_g || !w->layers[l].kn_g) return visrep_set_error(VISREP_ERR_ARG, "vit_forward_cpu: a qk_norm tower needs qn_g and kn_g in every layer");
     const long M = (long)B * T;
     const int dh = d / c->heads, mlp = c->mlp;
     const float* pw = (const float*)w->patch_w;
@@ -155,8 +209,10 @@ extern "C" int visrep_vit_forward_cpu(const visrep_vit_config* c, const visrep_v
     const float scale = 1.0f / sqrtf((float)dh);
     for (int l = 0; l < n_layers; ++l) {
         const visrep_vit_layer& L = w->layers[l];
-        layernorm_rows_cpu(hidden, L.ln1_g, L.ln1_b, h.data(), M, d, c->eps, threads);
+        if (rms) rmsnorm_rows_cpu(hidden, d, L.ln1_g, L.ln1_g, h.data(), d, M, d, 1, d, c->eps, threads);
+        else layernorm_rows_cpu(hidden, L.ln1_g, L.ln1_b, h.data(), M, d, c->eps, threads);
         linear_rows(h.data(), d, (const float*)L.wqkv, d, L.bqkv, qkv.data(), 3 * d, M, 3 * d, d, threads);
+        if (c->qk_norm) rmsnorm_rows_cpu(qkv.data(), 3 * d, L.qn_g, L.kn_g, qkv.data(), 3 * d, M, d, 2, d, VISREP_QK_NORM_EPS, threads);
         // softmax(q k^T / sqrt(dh)) v per (image, head, query row), fp32 with a max-subtracted exponent like torch.softmax
         parallel_for((long)B * c->heads, threads, [&](long bh) {
             const int b = (int)(bh / c->heads), hd = (int)(bh % c->heads);
@@ -187,7 +243,8 @@ extern "C" int visrep_vit_forward_cpu(const visrep_vit_config* c, const visrep_v
             for (long r = blk * 64; r < std::min<long>(M, blk * 64 + 64); ++r)
                 for (int i = 0; i < d; ++i) hidden[(size_t)r * d + i] += (L.ls1 ? L.ls1[i] : 1.f) * tmp[(size_t)r * d + i];
         });
-        layernorm_rows_cpu(hidden, L.ln2_g, L.ln2_b, h.data(), M, d, c->eps, threads);
+        if (rms) rmsnorm_rows_cpu(hidden, d, L.ln2_g, L.ln2_g, h.data(), d, M, d, 1, d, c->eps, threads);
+        else layernorm_rows_cpu(hidden, L.ln2_g, L.ln2_b, h.data(), M, d, c->eps, threads);
         linear_rows(h.data(), d, (const float*)L.w1, d, L.b1, mid.data(), mw, M, mw, d, threads);
         const int act = c->act;
         if (swiglu) {                                         // x1, x2 = chunk(2); silu(x1) * x2, left in the first mlp columns of each row

@@ -232,6 +232,18 @@ extern "C" int visrep_gemm_bf16_resid_stats(const void* A, int lda, const void* 
     return visrep_gemm_dispatch(a, (hipStream_t)stream);
 }
 
+extern "C" int visrep_gemm_bf16_resid_rms_stats(const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc, int M, int N,
+                                                int K, const void* resid, const float* ls, void* rt, void* partial, float eps, void* stream) {
+    if (!A || !W || !C || !resid || !rt || !partial) return visrep_set_error(VISREP_ERR_ARG, "gemm_resid_rms_stats: null pointer");
+    if (N > 4096 || N % 8) return visrep_set_error(VISREP_ERR_SHAPE, "gemm_resid_rms_stats: N <= 4096, N % 8 == 0");
+    if (ldc % 8 || ((uintptr_t)C & 15)) return visrep_set_error(VISREP_ERR_SHAPE, "gemm_resid_rms_stats: C must be 16-byte aligned with ldc % 8 == 0");
+    GemmArgs a{};
+    a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = (bf16_t*)C; a.bias = bias; a.resid = (const bf16_t*)resid; a.ls = ls;
+    a.stat_rt = (float2*)rt; a.stat_partial = (float2*)partial; a.stat_eps = eps; a.stat_rms = 1;
+    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.epi = EPI_RESID;
+    return visrep_gemm_dispatch(a, (hipStream_t)stream);
+}
+
 extern "C" int visrep_conv3x3_bf16(const void* x, int B, int H, int W, int C, const void* Wt, int ldw, const float* bias, void* out, int ldc,
                                    int Cout, int stride, int pad_mode, int upsample, int epilogue, const void* resid, void* stream) {
     if (!x || !Wt || !out) return visrep_set_error(VISREP_ERR_ARG, "conv3x3: null pointer");
@@ -359,6 +371,15 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
     if (grid * grid + prefix != c->tokens) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: tokens != grid^2 + cls + registers");
     if (c->has_cls && !w->cls) return visrep_set_error(VISREP_ERR_ARG, "vit_forward: a CLS tower needs the cls table");
     if (c->act < VISREP_ACT_NONE || c->act > VISREP_ACT_SWIGLU) return visrep_set_error(VISREP_ERR_ARG, "vit_forward: unknown activation code");
+    if (c->norm != 0 && c->norm != 1) return visrep_set_error(VISREP_ERR_ARG, "vit_forward: norm must be 0 (LayerNorm) or 1 (RMSNorm)");
+    const bool rms = c->norm == 1;
+    if (rms && c->pre_ln) return visrep_set_error(VISREP_ERR_ARG, "vit_forward: pre_ln with RMSNorm blocks is not supported");
+    if (rms && c->d > 4096) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: RMSNorm blocks need d <= 4096");
+    if (c->qk_norm) {
+        if (c->heads * dp > 4096) return visrep_set_error(VISREP_ERR_SHAPE, "vit_forward: qk_norm needs heads * head_pad <= 4096");
+        for (int l = 0; l < n_layers; ++l)
+            if (!w->layers[l].qn_g || !w->layers[l].kn_g) return visrep_set_error(VISREP_ERR_ARG, "vit_forward: a qk_norm tower needs qn_g and kn_g in every layer");
+    }
     hipStream_t s = (hipStream_t)stream;
     const Ws L = layout(c, B);
     char* base = (char*)workspace;
@@ -403,16 +424,18 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
         const bool fold_next = l + 1 < n_layers && w->layers[l + 1].sqkv && w->layers[l + 1].s1;   // and those by the GEMM that writes x
         GemmArgs a{};
         if (fold) {
-            if (!rt_ready) VR_TRY(visrep_layernorm_stats(x, d, rt, M, d, c->eps, stream));
+            if (!rt_ready) VR_TRY(rms ? visrep_rmsnorm_stats(x, d, rt, M, d, c->eps, stream) : visrep_layernorm_stats(x, d, rt, M, d, c->eps, stream));
             a.A = x; a.ln_rt = rt; a.ln_s = W.sqkv;
         } else {
-            VR_TRY(visrep_layernorm(x, d, W.ln1_g, W.ln1_b, h, d, M, d, c->eps, stream));
+            VR_TRY(rms ? visrep_rmsnorm(x, d, W.ln1_g, h, d, M, d, c->eps, stream) : visrep_layernorm(x, d, W.ln1_g, W.ln1_b, h, d, M, d, c->eps, stream));
             a.A = h;
         }
         a.lda = d; a.K = d; a.M = M;
         // Q | K projection
         a.W = (const bf16_t*)W.wqkv; a.ldw = d; a.N = 2 * da; a.C = qk; a.ldc = 2 * da; a.bias = W.bqkv; a.epi = EPI_BIAS;
         VR_TRY(visrep_gemm_dispatch(a, s));
+        // QK normalisation over the whole width, in place, before any attention route reads Q | K
+        if (c->qk_norm) VR_TRY(visrep_qk_rmsnorm(qk, 2 * da, da, d, W.qn_g, W.kn_g, M, VISREP_QK_NORM_EPS, stream));
         // V projection written transposed + perm16 for the attention kernel
         a.W = (const bf16_t*)W.wqkv + (size_t)2 * da * d; a.N = da; a.C = vt; a.ldc = L.ldvt; a.bias = W.bqkv + 2 * da; a.epi = EPI_VT;
         if (fold) a.ln_s = W.sqkv + 2 * da;
@@ -437,13 +460,13 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
         // out projection + LayerScale + residual (in place on x)
         a.A = h; a.lda = da; a.K = da; a.ldw = da; a.ln_rt = nullptr; a.ln_s = nullptr;
         a.W = (const bf16_t*)W.wo; a.N = d; a.C = x; a.ldc = d; a.bias = W.bo; a.epi = EPI_RESID; a.resid = x; a.ls = W.ls1;
-        if (fold) { a.stat_rt = rt; a.stat_partial = part; a.stat_eps = c->eps; }   // LN2's statistics come out of this GEMM
+        if (fold) { a.stat_rt = rt; a.stat_partial = part; a.stat_eps = c->eps; a.stat_rms = rms; }   // LN2's statistics come out of this GEMM
         VR_TRY(visrep_gemm_dispatch(a, s));
         GemmArgs f{};
         if (fold) {
             f.A = x; f.ln_rt = rt; f.ln_s = W.s1;
         } else {
-            VR_TRY(visrep_layernorm(x, d, W.ln2_g, W.ln2_b, h, d, M, d, c->eps, stream));
+            VR_TRY(rms ? visrep_rmsnorm(x, d, W.ln2_g, h, d, M, d, c->eps, stream) : visrep_layernorm(x, d, W.ln2_g, W.ln2_b, h, d, M, d, c->eps, stream));
             f.A = h;
         }
         f.lda = d; f.K = d; f.M = M; f.W = (const bf16_t*)W.w1; f.ldw = d; f.N = c->mlp; f.C = mlp; f.ldc = c->mlp;
@@ -464,7 +487,7 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
         f.ln_rt = nullptr; f.ln_s = nullptr;
         f.A = mlp; f.lda = c->mlp; f.K = c->mlp; f.W = (const bf16_t*)W.w2; f.ldw = c->mlp; f.N = d; f.C = x; f.ldc = d;
         f.bias = W.b2; f.epi = EPI_RESID; f.act = 0; f.resid = x; f.ls = W.ls2;
-        if (fold_next) { f.stat_rt = rt; f.stat_partial = part; f.stat_eps = c->eps; }   // the next layer's LN1
+        if (fold_next) { f.stat_rt = rt; f.stat_partial = part; f.stat_eps = c->eps; f.stat_rms = rms; }   // the next layer's LN1
         rt_ready = fold_next;
         VR_TRY(visrep_gemm_dispatch(f, s));
     }

@@ -75,6 +75,9 @@ struct GemmArgs {
     int walk;                       // v5 tile walk (set by the launcher from t_visrep_gemm_walk): 0 = default; low byte C > 0 = column-group-major walk, C columns per group
     unsigned long long* dbg_buf;    // timing-only: per-segment cycle sums (VISREP_GEMM_ABLATE builds)
     int dbg;                        // timing-only ablation mask for the v2 kernel (1 = no MFMA, 2 = no LDS-DMA, 4 = no ds_read); 0 in production
+    // stat_rt in its RMS form (visrep_vit_config::norm == 1): stat_rt[m] = (rsqrt(mean(x^2) + eps), 0), from the sum-of-squares slot of the same
+    // partial sums.  Read on the host and by splitk_reduce_rms only; last member, so that no existing kernel's argument offsets move.
+    int stat_rms;
 };
 
 struct VisrepXcdSlot { unsigned long long t_end[8]; unsigned long long t_start; unsigned done, pad; };   // 100-MHz ticks (s_memrealtime)
@@ -90,6 +93,7 @@ __device__ __forceinline__ int visrep_a_row(const GemmArgs& p, int r) {         
 #endif
 int visrep_gemm_dispatch(const GemmArgs& a, hipStream_t s);
 int visrep_ln_stats_finalize(const float2* partial, int slots, float2* rt, int rows, int d, float eps, hipStream_t s);
+int visrep_rms_stats_finalize(const float2* partial, int slots, float2* rt, int rows, int d, float eps, hipStream_t s);
 bool visrep_gemm_v2_supports(const GemmArgs& a);
 int visrep_gemm_v2_dispatch(const GemmArgs& a, hipStream_t s);
 bool visrep_gemm_v4_supports(const GemmArgs& a);

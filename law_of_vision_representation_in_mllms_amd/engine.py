@@ -59,6 +59,15 @@ def pad_tower_weights(spec: ViTSpec, layer: dict, dp: int, mp: int) -> dict:
     return L
 
 
+def pad_qk_gain(spec: ViTSpec, g: Optional[torch.Tensor], dp: int) -> torch.Tensor:
+    """A QK-norm weight [d] (None = ones) with every head zero-padded to `dp` lanes -> [heads dp] (fp32): the padded Q / K columns are zero
+    before the norm (pad_tower_weights) and, with a zero gain, stay zero behind it.  visrep_qk_rmsnorm divides the sum of squares by the TRUE width d."""
+    H, dh = spec.heads, spec.d // spec.heads
+    out = torch.zeros(H, dp)
+    out[:, :dh] = 1.0 if g is None else g.detach().float().reshape(H, dh)
+    return out.reshape(H * dp)
+
+
 def swiglu_interleave_index(mp: int) -> torch.Tensor:
     """Row order of the gated GEMM (visrep_gemm_bf16_gated) in terms of HF chunk order [gate 0 .. mp | value 0 .. mp]: GEMM row 32 t + r is the
     gate row of hidden unit 16 t + r, row 32 t + 16 + r its value row (r < 16).  `x[idx]` interleaves, `out[idx] = y` undoes it."""
@@ -98,6 +107,8 @@ class VitEngine:
         """head_pad: lanes per head in the device buffers, None = head_pad_for(d / heads) (64 -> 64, 65 .. 96 -> 96, 97 .. 128 -> 128);
         128 for a head of 65 .. 96 is the route attn_fwd96 replaced (attn_fwd<2> on heads padded to 128), kept reachable for A/B runs.
         The MLP width is padded to a multiple of 128 alike (pad_tower_weights).
+        RMSNorm towers (spec.norm == "rmsnorm") take the same two routes with visrep_rmsnorm_stats / visrep_rmsnorm; QK-norm towers
+        (spec.qk_norm) carry qn_g / kn_g padded per head, the pre-scaled-Q constant on qn_g instead of on the Q rows.
         fuse_ln (default on; VISREP_FUSE_LN=0 turns it off): fold every block's LayerNorm into the GEMMs that consume it -
         gamma into the weight rows, beta into the bias, the per-row mean / rstd into the GEMM epilogue (ln_rt / ln_s) - so the
         normalised activations are never written to HBM, and take the row statistics from the epilogue of the residual GEMM that
@@ -156,9 +167,11 @@ class VitEngine:
         # Padded heads (head_pad 96 / 128) keep the scale in the kernel: the pre-scaled variant of the flash kernel is built for width 64 only.
         self._q_mode = int(os.environ.get("VISREP_Q_PRESCALE", "2")) if self.head_pad == 64 else 0
         self.q_prescaled = self._q_mode != 0
+        # QK-norm towers (InternViT-6B): a norm behind the projection would undo a constant folded into the Q rows, so it goes into qn_g instead
         qc = torch.ones(3 * da)
-        if self.q_prescaled:
-            qc[: da] = self.head_dim ** -0.5 * 1.4426950408889634
+        q_const = self.head_dim ** -0.5 * 1.4426950408889634
+        if self.q_prescaled and not spec.qk_norm:
+            qc[: da] = q_const
 
         def fold(Wm, bias, g, b, rowscale=None):
             """Linear(LayerNorm(x)) = rstd * (x (g o W)^T - mean * s) + (W b + bias): (g o W in bf16, s over the ROUNDED rows, b').
@@ -173,10 +186,11 @@ class VitEngine:
             ent = self._layers[i]
             L = pad_tower_weights(spec, L, self.head_pad, self.mlp_pad)       # before the fold: it sees the padded matrices (zero rows: s = 0, b' = 0)
             extra = {"sqkv": None, "s1": None}
-            if self.fuse_ln:
-                L["wqkv"], extra["sqkv"], L["bqkv"] = fold(L["wqkv"], L.get("bqkv"), L["ln1_g"], L["ln1_b"], qc)
-                L["w1"], extra["s1"], L["b1"] = fold(L["w1"], L.get("b1"), L["ln2_g"], L["ln2_b"])
-            elif self.q_prescaled:                                             # unfused path: scale the (bf16-rounded) rows, round once more
+            if self.fuse_ln:                                                   # RMSNorm blocks: gamma only, no beta term (sqkv / s1 stay finite and meet a zero factor)
+                nb = torch.zeros(spec.d) if spec.norm == "rmsnorm" else None
+                L["wqkv"], extra["sqkv"], L["bqkv"] = fold(L["wqkv"], L.get("bqkv"), L["ln1_g"], L["ln1_b"] if nb is None else nb, qc)
+                L["w1"], extra["s1"], L["b1"] = fold(L["w1"], L.get("b1"), L["ln2_g"], L["ln2_b"] if nb is None else nb)
+            elif self.q_prescaled and not spec.qk_norm:                        # unfused path: scale the (bf16-rounded) rows, round once more
                 L["wqkv"] = L["wqkv"].detach().float().to(torch.bfloat16).float() * qc[:, None]
                 if L.get("bqkv") is not None:
                     L["bqkv"] = L["bqkv"].detach().float() * qc
@@ -195,6 +209,9 @@ class VitEngine:
             for k, t in extra.items():
                 v = vec(t)
                 setattr(ent, k, 0 if v is None else v.data_ptr())
+            if spec.qk_norm:                                                   # fp32 gains, padded per head; the pre-scaled-Q constant rides on qn_g
+                ent.qn_g = vec(pad_qk_gain(spec, L.get("qn_g"), self.head_pad) * (q_const if self.q_prescaled else 1.0)).data_ptr()
+                ent.kn_g = vec(pad_qk_gain(spec, L.get("kn_g"), self.head_pad)).data_ptr()
         self._w = _lib.VitWeights()
         self._w.patch_w = self._patch_w.data_ptr()
         for k, v in self._vecs.items():
@@ -202,7 +219,7 @@ class VitEngine:
         self._w.layers = C.cast(self._layers, C.POINTER(_lib.VitLayer))
         self._cfg = _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, self.mlp_pad, n, spec.tokens,
                                    int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), self._q_mode,
-                                   self.head_dim, self.head_pad, spec.registers)
+                                   self.head_dim, self.head_pad, spec.registers, _lib.NORM[spec.norm], int(spec.qk_norm))
         self._ws: Dict[int, torch.Tensor] = {}
         self._pinned = set()                 # batch sizes whose workspace a captured HIP graph refers to
 
@@ -298,6 +315,8 @@ class VitEngineF32:
             for k in ("wqkv", "wo", "w1", "w2", "ln1_g", "ln1_b", "bqkv", "bo", "ls1", "ln2_g", "ln2_b", "b1", "b2", "ls2"):
                 v = f32(L.get(k))
                 setattr(ent, k, 0 if v is None else v.data_ptr())
+            if spec.qk_norm:                                                   # absent gains = ones
+                ent.qn_g, ent.kn_g = (f32(L[k] if L.get(k) is not None else torch.ones(spec.d)).data_ptr() for k in ("qn_g", "kn_g"))
             ent.sqkv = 0
             ent.s1 = 0
         self._w = _lib.VitWeights()
@@ -306,7 +325,8 @@ class VitEngineF32:
             setattr(self._w, k, 0 if v is None else v.data_ptr())
         self._w.layers = C.cast(self._layers, C.POINTER(_lib.VitLayer))
         self._cfg = _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, spec.mlp, n, spec.tokens,
-                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), registers=spec.registers)
+                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), registers=spec.registers,
+                                   norm=_lib.NORM[spec.norm], qk_norm=int(spec.qk_norm))
         self._ws: Dict[int, torch.Tensor] = {}
         self._pinned = set()                 # batch sizes whose workspace a captured HIP graph refers to
         import os
@@ -315,7 +335,7 @@ class VitEngineF32:
             raise ValueError(f"gemm must be 'auto', 'split' or 'native', got {gemm!r}")
         can = bool(self.lib.visrep_vit_f32_split_supported(C.byref(self._cfg)))
         if gemm == "split" and not can:
-            raise ValueError("split-bf16 route needs d and mlp to be multiples of 256 and head width 64")
+            raise ValueError("split-bf16 route needs d and mlp to be multiples of 256, head width 64 and LayerNorm blocks without QK norm")
         self.gemm = "split" if (gemm != "native" and can) else "native"
         products = int(os.environ.get("VISREP_F32_PRODUCTS", products if products is not None else DEFAULT_SPLIT_PRODUCTS))
         if products not in (3, 4, 6):
@@ -458,6 +478,8 @@ class VitEngineCPU:
             for k in ("wqkv", "wo", "w1", "w2", "ln1_g", "ln1_b", "bqkv", "bo", "ls1", "ln2_g", "ln2_b", "b1", "b2", "ls2"):
                 v = f32(L.get(k))
                 setattr(ent, k, 0 if v is None else v.data_ptr())
+            if spec.qk_norm:                                                   # absent gains = ones
+                ent.qn_g, ent.kn_g = (f32(L[k] if L.get(k) is not None else torch.ones(spec.d)).data_ptr() for k in ("qn_g", "kn_g"))
             ent.sqkv = 0
             ent.s1 = 0
         self._w = _lib.VitWeights()
@@ -466,7 +488,8 @@ class VitEngineCPU:
             setattr(self._w, k, 0 if v is None else v.data_ptr())
         self._w.layers = C.cast(self._layers, C.POINTER(_lib.VitLayer))
         self._cfg = _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, spec.mlp, n, spec.tokens,
-                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), registers=spec.registers)
+                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), registers=spec.registers,
+                                   norm=_lib.NORM[spec.norm], qk_norm=int(spec.qk_norm))
 
     @torch.no_grad()
     def forward(self, pixels: torch.Tensor, n_layers: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:

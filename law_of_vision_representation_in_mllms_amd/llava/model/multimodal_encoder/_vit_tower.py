@@ -136,6 +136,9 @@ class HipViTTower(nn.Module):
             spec = VW.spec_from_hf_config(cfg, self.vision_tower_name, crop_size=_processor_crop(path))
             sd = _load_state_dict(path)
             sd = {k: v for k, v in sd.items() if not k.startswith(("text_model.", "logit_", "text_projection", "visual_projection"))}
+            if spec.family == "internvl" and any(k.startswith(("model.vision_tower.", "vision_tower.")) for k in sd):
+                # an InternVL checkpoint (either key layout): only the tower's tensors reach the packer, the language model is never touched
+                sd = {k: v for k, v in sd.items() if k.startswith(("model.vision_tower.", "vision_tower."))}
             return spec, VW.pack_hf_state_dict(sd, spec)
         if self._synthetic and self.vision_tower_name in VW.SPECS:
             spec = VW.SPECS[self.vision_tower_name]
@@ -150,7 +153,13 @@ class HipViTTower(nn.Module):
         path = _find_local_checkpoint(self.vision_tower_name)
         if path is not None:
             from transformers import AutoConfig
-            return AutoConfig.from_pretrained(path)
+            cfg = AutoConfig.from_pretrained(path)
+            if getattr(cfg, "model_type", "") in ("internvl", "internvl_vision"):
+                # an InternVL checkpoint: the tower is its vision_config, whose image_size / patch_size are pairs - the protocol wants integers
+                spec = VW.spec_from_hf_config(cfg, self.vision_tower_name)
+                return SimpleNamespace(hidden_size=spec.d, image_size=spec.image_size, patch_size=spec.patch, num_hidden_layers=spec.layers,
+                                       num_attention_heads=spec.heads, intermediate_size=spec.mlp)
+            return cfg
         if self.vision_tower_name not in VW.SPECS:           # like from_pretrained on a name that is neither a directory nor cached
             raise OSError(f"{self.vision_tower_name} is not a local checkpoint directory, is not in the offline HF cache and has no built-in "
                           "architecture")

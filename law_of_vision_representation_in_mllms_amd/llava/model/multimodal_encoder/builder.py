@@ -11,6 +11,7 @@ import os
 from .clip_encoder import CLIPVisionTower
 from .diffLVLM.diffusion_encoder import DiffVisionTower
 from .dinov2_encoder import DinoV2VisionTower
+from .internvit_encoder import InternViTVisionTower
 from .siglip_encoder import SigLipVisionTower
 
 _CLIP_PREFIXES = ("openai", "laion")
@@ -38,6 +39,11 @@ def build_dinov2_vision_tower(vision_tower_cfg, **kwargs):
 
 def build_siglip_vision_tower(vision_tower_cfg, **kwargs):
     return _make(SigLipVisionTower, vision_tower_cfg, kwargs)
+
+
+def build_internvit_vision_tower(vision_tower_cfg, **kwargs):
+    """InternViT (the InternVL vision tower).  Not a reference registry entry: add the id to llava_arch.build_function_mapping."""
+    return _make(InternViTVisionTower, vision_tower_cfg, kwargs)
 
 
 def build_diffusion_vision_tower(vision_tower_cfg, **kwargs):

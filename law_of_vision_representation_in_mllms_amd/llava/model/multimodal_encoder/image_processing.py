@@ -58,4 +58,6 @@ def default_image_processor(spec):
         return SimpleImageProcessor(spec.image_size, spec.image_size, OPENAI_CLIP_MEAN, OPENAI_CLIP_STD)
     if spec.family == "dinov2":
         return SimpleImageProcessor(int(round(spec.image_size * 256 / 224)), spec.image_size, IMAGENET_MEAN, IMAGENET_STD)
+    if spec.family == "internvl":                             # InternVL's processor: square resize to the tower's size, ImageNet statistics
+        return SimpleImageProcessor(spec.image_size, spec.image_size, IMAGENET_MEAN, IMAGENET_STD, square_resize=True)
     return SimpleImageProcessor(spec.image_size, spec.image_size, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5), square_resize=True)

@@ -15,6 +15,9 @@ Packed layout (fp32 torch tensors on CPU):
              ln2_g ln2_b w1[m,d] b1[m] w2[d,m] b2[d] ls2[d]|None
   act "swiglu" (HF Dinov2SwiGLUFFN): m = spec.mlp is the hidden width h, w1 [2h, d] / b1 [2h] are weights_in in HF order
   (the h gate rows x1, then the h value rows x2), w2 [d, h] is weights_out.
+  norm "rmsnorm" (HF InternVLVisionRMSNorm, InternViT-6B): ln*_g are the RMSNorm weights; ln*_b are ignored (the packer writes zeros).
+  qk_norm (HF InternVLVisionAttention, use_qk_norm): layers[i] also carry qn_g / kn_g [d], the weights of the RMSNorm over the WHOLE
+  embedding width that follows q_proj / k_proj (before the head split; eps QK_NORM_EPS whatever the block norm's eps is); absent = ones.
 """
 from __future__ import annotations
 
@@ -40,13 +43,19 @@ class ViTSpec:
     pre_ln: bool        # CLIP pre_layrnorm
     patch_bias: bool
     layerscale: bool    # DINOv2
-    family: str         # clip | dinov2 | siglip
+    family: str         # clip | dinov2 | siglip | internvl
     pos_grid: int = 0   # native position-embedding grid (DINOv2: 37); 0 = image_size // patch
     registers: int = 0  # register tokens between the CLS row and the patch rows (HF Dinov2WithRegisters: num_register_tokens)
+    norm: str = "layernorm"   # layernorm | rmsnorm: the two pre-block norms (HF InternVLVisionConfig.norm_type)
+    qk_norm: bool = False     # RMSNorm over the whole embedding width behind q_proj and k_proj (HF InternVLVisionConfig.use_qk_norm)
 
     def __post_init__(self):
         if self.registers < 0 or (self.registers > 0 and not self.has_cls):
             raise ValueError("register tokens need a CLS token (registers >= 0, has_cls)")
+        if self.norm not in ("layernorm", "rmsnorm"):
+            raise ValueError(f"norm must be 'layernorm' or 'rmsnorm', got {self.norm!r}")
+        if self.norm == "rmsnorm" and self.pre_ln:
+            raise ValueError("a pre-LayerNorm tower with RMSNorm blocks is not supported (no known tower has both)")
 
     @property
     def fc1_rows(self) -> int:
@@ -102,7 +111,16 @@ SPECS: Dict[str, ViTSpec] = {
                                                     "gelu", 1e-6, True, False, True, True, "dinov2", pos_grid=37, registers=4),
     "facebook/dinov2-with-registers-giant": ViTSpec("facebook/dinov2-with-registers-giant", 224, 14, 1536, 40, 24, 4096,
                                                     "swiglu", 1e-6, True, False, True, True, "dinov2", pos_grid=37, registers=4),
+    # InternViT (HF InternVLVisionModel, the vision tower of the InternVL family): CLS + 32 x 32 patches at 448 px, LayerScale, qkv bias only on
+    # the 300M tower; the 6B tower has RMSNorm blocks and an RMSNorm over the whole width behind q_proj / k_proj.  As recalled from the public
+    # configs; a local `config.json` wins.
+    "OpenGVLab/InternViT-300M-448px-V2_5": ViTSpec("OpenGVLab/InternViT-300M-448px-V2_5", 448, 14, 1024, 24, 16, 4096,
+                                                   "gelu", 1e-6, True, False, True, True, "internvl"),
+    "OpenGVLab/InternViT-6B-448px-V2_5": ViTSpec("OpenGVLab/InternViT-6B-448px-V2_5", 448, 14, 3200, 45, 25, 12800,
+                                                 "gelu", 1e-6, True, False, True, True, "internvl", norm="rmsnorm", qk_norm=True),
 }
+
+QK_NORM_EPS = 1e-6   # HF InternVLVisionAttention builds q_norm / k_norm as InternVLVisionRMSNorm(embed_dim): the class default, not layer_norm_eps
 
 
 def swiglu_hidden(d: int, mlp_ratio: float) -> int:
@@ -114,13 +132,13 @@ def tiny_spec(family: str, act: Optional[str] = None, image_size: int = 28, patc
               layers: int = 3, heads: int = 2, mlp: int = 128, registers: int = 0) -> ViTSpec:
     """Small spec of a given family for fixtures / tests."""
     base = {"clip": SPECS["openai/clip-vit-large-patch14"], "dinov2": SPECS["facebook/dinov2-large"],
-            "siglip": SPECS["google/siglip-base-patch16-224"]}[family]
+            "siglip": SPECS["google/siglip-base-patch16-224"], "internvl": SPECS["OpenGVLab/InternViT-300M-448px-V2_5"]}[family]
     return replace(base, name=f"tiny-{family}", image_size=image_size, patch=patch, d=d, layers=layers,
                    heads=heads, mlp=mlp, act=act or base.act, pos_grid=0, registers=registers)
 
 
 def spec_from_hf_config(cfg, name: str = "", crop_size: Optional[int] = None) -> ViTSpec:
-    """Build a spec from a HF CLIPVisionConfig / Dinov2Config / SiglipVisionConfig.
+    """Build a spec from a HF CLIPVisionConfig / Dinov2Config / SiglipVisionConfig / InternVLVisionConfig (or InternVLConfig: its vision_config).
 
     DINOv2: `cfg.image_size` (518 for facebook/dinov2-*) is the NATIVE position-embedding grid (37 x 37), not the input size the
     reference runs: its AutoImageProcessor resizes to 256 and centre-crops to `crop_size` (224 by default,
@@ -128,7 +146,7 @@ def spec_from_hf_config(cfg, name: str = "", crop_size: Optional[int] = None) ->
     processor's crop size (`crop_size`, read from preprocessor_config.json by the caller; 224 when absent) and only `pos_grid`
     keeps the native size."""
     mt = getattr(cfg, "model_type", "")
-    if hasattr(cfg, "vision_config") and mt in ("clip", "siglip"):
+    if hasattr(cfg, "vision_config") and mt in ("clip", "siglip", "internvl"):
         cfg = cfg.vision_config
         mt = cfg.model_type
     act = {"quick_gelu": "quick_gelu", "gelu": "gelu", "gelu_pytorch_tanh": "gelu_tanh", "gelu_new": "gelu_tanh",
@@ -150,6 +168,20 @@ def spec_from_hf_config(cfg, name: str = "", crop_size: Optional[int] = None) ->
         return ViTSpec(name, cfg.image_size, cfg.patch_size, cfg.hidden_size, cfg.num_hidden_layers,
                        cfg.num_attention_heads, cfg.intermediate_size, act, cfg.layer_norm_eps,
                        False, False, True, False, "siglip")
+    if mt == "internvl_vision":
+        def side(v, what):
+            a, b = (v, v) if isinstance(v, int) else tuple(v)
+            if a != b:
+                raise ValueError(f"InternViT: non-square {what} {tuple(v)} is not supported")
+            return int(a)
+        if not getattr(cfg, "use_absolute_position_embeddings", True):
+            raise ValueError("InternViT: use_absolute_position_embeddings = False is not supported (the tower adds a learned position table)")
+        norm = {"layer_norm": "layernorm", "rms_norm": "rmsnorm"}.get(cfg.norm_type)
+        if norm is None:
+            raise ValueError(f"InternViT: unsupported norm_type {cfg.norm_type!r}")
+        return ViTSpec(name, side(cfg.image_size, "image_size"), side(cfg.patch_size, "patch_size"), cfg.hidden_size, cfg.num_hidden_layers,
+                       cfg.num_attention_heads, cfg.intermediate_size, act, cfg.layer_norm_eps, True, False, True, True, "internvl",
+                       norm=norm, qk_norm=bool(cfg.use_qk_norm))           # use_mask_token only adds a parameter the forward never reads
     raise ValueError(f"unsupported HF model_type {mt!r}")
 
 
@@ -190,7 +222,8 @@ def pos_with_registers(pos: torch.Tensor, registers: int) -> torch.Tensor:
 
 
 def pack_hf_state_dict(sd: Dict[str, torch.Tensor], spec: ViTSpec) -> dict:
-    """HF CLIPVisionModel / Dinov2Model / SiglipVisionModel(.vision_model) state_dict -> packed layout."""
+    """HF CLIPVisionModel / Dinov2Model / SiglipVisionModel(.vision_model) / InternVLVisionModel (bare, or the vision_tower of an InternVL
+    checkpoint) state_dict -> packed layout."""
     d = spec.d
     if spec.family == "clip":
         s = _strip(sd, ["vision_model."])
@@ -228,6 +261,26 @@ def pack_hf_state_dict(sd: Dict[str, torch.Tensor], spec: ViTSpec) -> dict:
         lay = lambda i, k: s[f"encoder.layer.{i}.{k}"]
         names = dict(q="attention.attention.query", k="attention.attention.key", v="attention.attention.value",
                      o="attention.output.dense", ln1="norm1", ln2="norm2", fc1="mlp.fc1", fc2="mlp.fc2")
+    elif spec.family == "internvl":
+        s = _strip(sd, ["model.vision_tower.", "vision_tower.", "internvl_vision."])
+        w = {
+            "patch_w": s["embeddings.patch_embeddings.projection.weight"].reshape(d, -1),
+            "patch_b": s["embeddings.patch_embeddings.projection.bias"],
+            "cls": s["embeddings.cls_token"].reshape(d),
+            "pos": s["embeddings.position_embeddings"].reshape(-1, d),
+            "pre_ln_g": None, "pre_ln_b": None,
+        }
+        zeros = torch.zeros(d)
+
+        def lay(i, k):                                           # attention_bias = False: no q / k / v bias; rms_norm: no norm bias
+            t = s.get(f"encoder.layer.{i}.{k}")
+            if t is None and k.endswith(".bias") and k.split(".")[-2] in ("q_proj", "k_proj", "v_proj", "layernorm_before", "layernorm_after"):
+                return zeros
+            if t is None:
+                raise KeyError(f"encoder.layer.{i}.{k}")
+            return t
+        names = dict(q="attention.q_proj", k="attention.k_proj", v="attention.v_proj", o="attention.projection_layer",
+                     ln1="layernorm_before", ln2="layernorm_after", fc1="mlp.fc1", fc2="mlp.fc2")
     else:
         raise ValueError(spec.family)
     if spec.act == "swiglu":                                     # HF Dinov2SwiGLUFFN: weights_in [2h, d] (chunk order), weights_out [d, h]
@@ -250,16 +303,24 @@ def pack_hf_state_dict(sd: Dict[str, torch.Tensor], spec: ViTSpec) -> dict:
             "w2": lay(i, names["fc2"] + ".weight"), "b2": lay(i, names["fc2"] + ".bias"),
             "ls1": None, "ls2": None,
         }
-        if spec.layerscale:
+        if spec.layerscale and spec.family == "internvl":
+            L["ls1"], L["ls2"] = lay(i, "lambda_1"), lay(i, "lambda_2")
+        elif spec.layerscale:
             L["ls1"] = lay(i, "layer_scale1.lambda1")
             L["ls2"] = lay(i, "layer_scale2.lambda1")
+        if spec.qk_norm:
+            L["qn_g"], L["kn_g"] = lay(i, names["q"][:-4] + "norm.weight"), lay(i, names["k"][:-4] + "norm.weight")
         layers.append(L)
     w["layers"] = layers
     return w
 
 
-def synthetic_weights(spec: ViTSpec, seed: int = 1, n_layers: Optional[int] = None) -> dict:
+def synthetic_weights(spec: ViTSpec, seed: int = 1, n_layers: Optional[int] = None, qk_gains: bool = False) -> dict:
     """Deterministic random-init weights (numpy RandomState: stream frozen across versions).
+
+    The stream and the keys depend on the shapes and on `registers` only: a spec with RMSNorm blocks keeps its ln*_b draws (RMSNorm has no
+    bias: every engine ignores them) and a QK-norm spec gets unit gains - no qn_g / kn_g entries, which the engines read as ones - unless
+    qk_gains=True draws them (around 1, after everything else, as `reg` is).
 
     Scales are chosen so activations stay O(1) through 24 layers (std 0.02 matrices,
     LN gains around 1, LayerScale around 0.1 for DINOv2-style towers).
@@ -299,6 +360,9 @@ def synthetic_weights(spec: ViTSpec, seed: int = 1, n_layers: Optional[int] = No
         w["reg"] = rn(spec.registers, d)
         w["pos"] = w["pos"].clone()
         w["pos"][1:1 + spec.registers] = 0.0                     # registers carry no position term
+    if spec.qk_norm and qk_gains:                                # drawn after everything else, like `reg`
+        for L in layers:
+            L["qn_g"], L["kn_g"] = rn(d, std=0.1, mean=1.0), rn(d, std=0.1, mean=1.0)
     return w
 
 
@@ -368,11 +432,12 @@ def hostile_weights(spec: ViTSpec, seed: int = 1, n_layers: Optional[int] = None
       * LayerScale (DINOv2 family) spread log-uniformly over `ls_range` (1e-5 .. 1) with random signs (outlier channels keep 0.5 so that
         the planted activations survive);
       * sharp attention heads: the Q and K rows of two heads scaled by `sharp` (5) in every third layer - logits x25: near-one-hot softmax
-        rows with large pre-softmax scores (the pre-scaled-Q / running-reference paths of the attention kernels).
+        rows with large pre-softmax scores (the pre-scaled-Q / running-reference paths of the attention kernels);
+      * QK-norm towers (spec.qk_norm): qn_g / kn_g spread log-uniformly over 0.02 .. 3 with random signs.
     Returns the packed dict plus w["hostile"] = {"profile", "channels", "factors", "const_token", ...} for the tests' own assertions."""
     if profile not in ("outlier", "const", "all"):
         raise ValueError(f"profile must be 'outlier', 'const' or 'all', got {profile!r}")
-    w = synthetic_weights(spec, seed=seed, n_layers=n_layers)
+    w = synthetic_weights(spec, seed=seed, n_layers=n_layers)           # (QK-norm gains: planted below, not drawn here)
     rs = np.random.RandomState(seed + 7919)
     d, n = spec.d, len(w["layers"])
     ch = np.sort(rs.choice(d, n_outlier, replace=False))
@@ -411,6 +476,12 @@ def hostile_weights(spec: ViTSpec, seed: int = 1, n_layers: Optional[int] = None
                 for base in (0, d):                                  # Q rows, K rows of the head
                     L["wqkv"][base + hd * dh: base + (hd + 1) * dh] *= sharp
                     L["bqkv"][base + hd * dh: base + (hd + 1) * dh] *= sharp
+    if spec.qk_norm:                                                 # gains spread log-uniformly over 0.02 .. 3 with random signs (after every other draw)
+        for L in w["layers"]:
+            for k in ("qn_g", "kn_g"):
+                mag = np.exp(rs.uniform(np.log(0.02), np.log(3.0), d)).astype(np.float32)
+                sgn = np.where(rs.rand(d) < 0.5, -1.0, 1.0).astype(np.float32)
+                L[k] = torch.from_numpy(mag * sgn)
     tok = None
     if profile in ("const", "all"):
         tok = min(int(const_token) + spec.prefix, spec.tokens - 1)

@@ -11,6 +11,9 @@
   4. the gated (SwiGLU, EPI_GATED = 7) instantiations of both persistent GEMMs exist and obey 1 and 2 with NO scratch at all: their epilogue adds
      no row loads, so a spill there would be a regression of the epilogue itself.
 
+  5. the RMSNorm / QK-norm kernels of the InternViT towers (rowops.hip: rms_rows, rms_stats_rows, rms_stats_finalize_rows, qk_rmsnorm_rows,
+     rms_f32_rows; gemm_bf16.hip: splitk_reduce_rms) exist and use no scratch: a row of up to 4096 columns lives in 64 registers per lane.
+
 usage: python tools/isa_check.py [--sizes] [file.hip ...]      (default: the product library's persistent kernels)
 --sizes also prints every kernel's code length (to compare the existing instantiations with a parent build)."""
 import os
@@ -22,10 +25,12 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "law_of_vision_representation_in_mllms_amd", "csrc")
 SIZES = "--sizes" in sys.argv[1:]
-FILES = [a for a in sys.argv[1:] if a != "--sizes"] or ["gemm_bf16_v5.hip", "gemm_bf16_v2.hip", "ascore.hip", "attention.hip"]
+FILES = [a for a in sys.argv[1:] if a != "--sizes"] or ["gemm_bf16_v5.hip", "gemm_bf16_v2.hip", "ascore.hip", "attention.hip", "rowops.hip", "gemm_bf16.hip"]
 # kernels (by name fragment) that must not touch scratch; Li7E = template argument EPI_GATED of gemm_bf16_256q / gemm_bf16_256
-NO_SCRATCH = ("attn_fwd", "gemm_bf16_256qILi7E", "gemm_bf16_256ILi7E")
-REQUIRED = {"gemm_bf16_v5.hip": ("gemm_bf16_256qILi7ELb1E", "gemm_bf16_256qILi7ELb0E"), "gemm_bf16_v2.hip": ("gemm_bf16_256ILi7E",)}
+RMS_KERNELS = ("8rms_rows", "14rms_stats_rows", "23rms_stats_finalize_rows", "15qk_rmsnorm_rows", "12rms_f32_rows")
+NO_SCRATCH = ("attn_fwd", "gemm_bf16_256qILi7E", "gemm_bf16_256ILi7E", "17splitk_reduce_rms") + RMS_KERNELS
+REQUIRED = {"gemm_bf16_v5.hip": ("gemm_bf16_256qILi7ELb1E", "gemm_bf16_256qILi7ELb0E"), "gemm_bf16_v2.hip": ("gemm_bf16_256ILi7E",),
+            "rowops.hip": RMS_KERNELS, "gemm_bf16.hip": ("17splitk_reduce_rms",)}
 bad = 0
 for f in FILES:
     with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
@@ -56,7 +61,7 @@ for f in FILES:
             size[kernel] = int(m.group(1))
     for frag in REQUIRED.get(os.path.basename(f), ()):
         if not any(frag in k for k in scratch):
-            print(f"{f}: no kernel matching {frag} (the gated instantiation is missing)")
+            print(f"{f}: no kernel matching {frag} (a required instantiation is missing)")
             bad += 1
     if SIZES:
         for k in sorted(size):
