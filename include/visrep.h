@@ -96,7 +96,12 @@ enum {
     VISREP_ROUTE_STATS_ROWS = 16,    /* the read-only statistics pass over bf16 rows (visrep_layernorm_stats / visrep_rmsnorm_stats, called or fallen back to) */
     VISREP_ROUTE_RMS = 17,           /* any of the above, or a visrep_rmsnorm pass, in its RMS form */
     VISREP_ROUTE_QK_NORM = 18,       /* qk_rmsnorm_rows (visrep_qk_rmsnorm) */
-    VISREP_ROUTE_COUNT = 19
+    /* ConvNeXt towers (dwconv.hip).  New ids only: 0 .. 18 keep their meaning, and the version stays 650 - no struct or signature changed */
+    VISREP_ROUTE_DWCONV_16 = 19,     /* dwconv7x7_stats_tile<16, 16>: the depthwise 7x7 convolution on 16 x 16 output tiles */
+    VISREP_ROUTE_DWCONV_8 = 20,      /* dwconv7x7_stats_tile<8, 8>: the same on 8 x 8 tiles (small or ragged maps) */
+    VISREP_ROUTE_DWCONV_FINALIZE = 21, /* the statistics finalize behind either (ln_stats_finalize_rows, or its odd-slot form) */
+    VISREP_ROUTE_LN_S2D = 22,        /* ln_space_to_depth2_rows (visrep_ln_space_to_depth2) */
+    VISREP_ROUTE_COUNT = 23
 };
 int visrep_debug_routes(long* out, int reset);
 /* Matrix-pipe ceiling of THIS device under THIS process' conditions: `iters` bursts of 32 dependent-free v_mfma_f32_16x16x32_bf16 per wave,
@@ -351,6 +356,55 @@ int visrep_qk_rmsnorm_f32(float* qk, int ldqk, int width, int d_true, const floa
 int visrep_rmsnorm_cpu(const float* x, int ldx, const float* gamma, float* y, int ldy, long rows, int d, float eps, int threads);
 int visrep_rmsnorm_stats_cpu(const float* x, int ldx, float* rt, long rows, int d, float eps, int threads);
 int visrep_qk_rmsnorm_cpu(float* qk, int ldqk, int width, int d_true, const float* qn_g, const float* kn_g, long rows, float eps, int threads);
+
+/* ---- ConvNeXt towers (HF ConvNextModel; OpenCLIP's timm ConvNeXt trunks).  A block is
+ *   x + ls * pwconv2(GELU(pwconv1(LayerNorm(dwconv7x7(x)))))
+ * on channels-last token rows (row = (b H + y) W + x): visrep_dwconv7x7_stats, then visrep_gemm_bf16_ln (VISREP_EPI_ACT, VISREP_ACT_GELU_ERF)
+ * on the raw convolution output with the statistics it left, then visrep_gemm_bf16 (VISREP_EPI_RESID, ls).  The normalised tensor is never written.
+ *
+ * visrep_dwconv7x7_stats: y[b, oy, ox, c] = bf16( bias[c] + sum_{ky, kx} wt[ky * 7 + kx, c] * x[b, oy + ky - 3, ox + kx - 3, c] ), zero outside the
+ * image (padding 3), cross-correlation as nn.Conv2d(groups = C) computes it; fp32 fused multiply-adds in tap order starting from the bias, one
+ * rounding.  x, y: [B, H, W, C] bf16 with leading dimensions ldx, ldy >= C (% 8 == 0; columns past C are neither read nor written); wt [49, C]
+ * fp32, tap-major; bias [C] fp32.  The same pass writes, for every output row and every slab of 64 channels, (sum, sum of squares) of the
+ * bf16-ROUNDED outputs into partial [B H W, C / 64] float2, and a second launch reduces them in slab order to rt[row] = (rstd, -mean * rstd)
+ * with var = E[x^2] - mean^2 in fp32 - the pair visrep_gemm_bf16_ln consumes (allocate round_up(rows, 128) + 8 entries, zero past the rows).
+ * C % 64 == 0; any H, W >= 1 (maps smaller than the window included), any B; a tile never reads across an image boundary.  y must not alias x.
+ * x, wt, bias, y 16-byte aligned.  Anything else is refused before any launch (VISREP_ERR_SHAPE / VISREP_ERR_ARG).
+ * visrep_ln_space_to_depth2: out[(b (H/2) + oy) (W/2) + ox, (i * 2 + j) * C + c] = bf16( LayerNorm(x[b, 2 oy + i, 2 ox + j, :])[c] ), the rows of
+ * a 2x2 stride-2 convolution's GEMM (weight [Cout, 4 C] in the same k order).  x [B, H, W, C] bf16 (ldx >= C), gamma / beta [C] fp32, out bf16
+ * (ldo >= 4 C).  H and W even; C % 8 == 0, C <= 4096; 16-byte aligned pointers; out must not alias x (x stays intact: it is a hidden state).
+ * The _cpu forms are host twins with the same contract on HOST pointers (bf16 storage in and out, the same fmaf chain; sums of the statistics
+ * in double) - threads <= 0: a default. */
+int visrep_dwconv7x7_stats(const void* x, int ldx, const float* wt, const float* bias, void* y, int ldy, void* partial, void* rt, int B, int H,
+                           int W, int C, float eps, void* stream);
+int visrep_ln_space_to_depth2(const void* x, int ldx, const float* gamma, const float* beta, void* out, int ldo, int B, int H, int W, int C,
+                              float eps, void* stream);
+int visrep_dwconv7x7_stats_cpu(const void* x, int ldx, const float* wt, const float* bias, void* y, int ldy, float* rt, int B, int H, int W, int C,
+                               float eps, int threads);
+int visrep_ln_space_to_depth2_cpu(const void* x, int ldx, const float* gamma, const float* beta, void* out, int ldo, int B, int H, int W, int C,
+                                  float eps, int threads);
+/* Composed tower: hidden_states[n_stages] of HF ConvNextModel(output_hidden_states=True) - index 0 = the stem (4x4 stride-4 convolution +
+ * LayerNorm), 1 .. 4 = the stage outputs - as token rows [B, H_s W_s, C_s] bf16 (H_s = image / 4 for index 0 and 1, halved per later stage).
+ * widths[s] % 64 == 0; wp(s) = widths[s] rounded up to 128 is the width of the GEMM OUTPUTS (the residual stream's leading dimension): stem_w
+ * [wp(0), kpad] (k = c 16 + i 4 + j, zero past 48), ds_w[s] [wp(s), 4 widths[s - 1]] (k = (i 2 + j) C + c), w2 [wp, 4 C], and stem_b / ds_b / b2 /
+ * ls [wp], all zero in the padded rows; w1 [4 C, C] = gamma o W with s1[n] = its row sums and b1 = W beta + b (the block LayerNorm folded, as for
+ * the ViT blocks); dw_w [49, C], dw_b [C].  ls may be NULL (no LayerScale).  ds_*[0] are unused.  image_size % 32 == 0.  bf16 only. */
+typedef struct {
+    int image_size, kpad;
+    int depths[4], widths[4];
+    float eps;
+} visrep_convnext_config;
+typedef struct {
+    const float *dw_w, *dw_b; const void* w1; const float *b1, *s1; const void* w2; const float *b2, *ls;
+} visrep_convnext_block;
+typedef struct {
+    const void* stem_w; const float *stem_b, *stem_ln_g, *stem_ln_b;
+    const float *ds_ln_g[4], *ds_ln_b[4]; const void* ds_w[4]; const float* ds_b[4];
+    const visrep_convnext_block* blocks;   /* HOST array of depths[0] + .. + depths[3] entries, stage by stage */
+} visrep_convnext_weights;
+size_t visrep_convnext_workspace_bytes(const visrep_convnext_config* cfg, int B);
+int visrep_convnext_forward(const visrep_convnext_config* cfg, const visrep_convnext_weights* w, const void* pixels, int pixel_dtype, void* hidden,
+                            int B, int n_stages, void* workspace, void* stream);
 
 /* ---- reference-precision (fp32) tower path.  The reference builds the C-score CLIP / OpenCLIP / DINOv2 towers with no dtype cast and
  * fp32 pixels (C_score/extract_feature.py:36-45,49-50,80-87): every tensor and accumulation here is fp32 (v_mfma_f32_32x32x2_f32 = an

@@ -37,6 +37,19 @@ class VitWeights(C.Structure):
         ("layers", C.POINTER(VitLayer))]
 
 
+class ConvNextConfig(C.Structure):
+    _fields_ = [("image_size", C.c_int), ("kpad", C.c_int), ("depths", C.c_int * 4), ("widths", C.c_int * 4), ("eps", C.c_float)]
+
+
+class ConvNextBlock(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("dw_w", "dw_b", "w1", "b1", "s1", "w2", "b2", "ls")]
+
+
+class ConvNextWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("stem_w", "stem_b", "stem_ln_g", "stem_ln_b")] + [
+        (n, C.c_void_p * 4) for n in ("ds_ln_g", "ds_ln_b", "ds_w", "ds_b")] + [("blocks", C.POINTER(ConvNextBlock))]
+
+
 class JpegInfo(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("ncomp", C.c_int), ("hs", C.c_int * 3), ("vs", C.c_int * 3), ("hmax", C.c_int),
                 ("vmax", C.c_int), ("mcus_w", C.c_int), ("mcus_h", C.c_int), ("blocks_w", C.c_int * 3), ("blocks_h", C.c_int * 3),
@@ -76,6 +89,12 @@ SIGNATURES = {
     "visrep_rmsnorm_cpu": (_i, [_vp, _i, _vp, _vp, _i, _l, _i, _f, _i]),
     "visrep_rmsnorm_stats_cpu": (_i, [_vp, _i, _vp, _l, _i, _f, _i]),
     "visrep_qk_rmsnorm_cpu": (_i, [_vp, _i, _i, _i, _vp, _vp, _l, _f, _i]),
+    "visrep_dwconv7x7_stats": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "visrep_ln_space_to_depth2": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "visrep_dwconv7x7_stats_cpu": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _i]),
+    "visrep_ln_space_to_depth2_cpu": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i]),
+    "visrep_convnext_workspace_bytes": (_sz, [C.POINTER(ConvNextConfig), _i]),
+    "visrep_convnext_forward": (_i, [C.POINTER(ConvNextConfig), C.POINTER(ConvNextWeights), _vp, _i, _vp, _i, _i, _vp, _vp]),
     "visrep_gemm_bf16_gated": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "visrep_swiglu": (_i, [_vp, _i, _vp, _i, _l, _i, _vp]),
     "visrep_swiglu_f32": (_i, [_vp, _i, _vp, _i, _l, _i, _vp]),
@@ -199,6 +218,10 @@ ROUTES = ("gemm_256", "gemm_128", "gemm_tail", "splitk", "conv_256", "conv_128",
           "stats_epilogue", "stats_reduce", "stats_rows", "rms", "qk_norm")
 
 
+# ConvNeXt launches (ids 19 .. 22).  Kept beside ROUTES, not inside it: the ids 0 .. 18 are the set the ViT / diffusion tests pin by position.
+CONVNEXT_ROUTES = ("dwconv_16", "dwconv_8", "dwconv_finalize", "ln_s2d")
+
+
 def xcd_balance() -> dict:
     """{"on": bool, "rel": [8 floats: smoothed time per round of tiles of each XCD relative to the mean], "updates": measurements folded in}
     of the current device's XCD-weighted tile split (visrep_debug_xcd_balance)."""
@@ -210,10 +233,11 @@ def xcd_balance() -> dict:
 
 def routes(reset: bool = False) -> dict:
     """This thread's launch counters per kernel family (visrep_debug_routes): {name: count}."""
-    buf = (C.c_long * len(ROUTES))()
+    names = ROUTES + CONVNEXT_ROUTES
+    buf = (C.c_long * len(names))()
     n = load().visrep_debug_routes(buf, int(reset))
-    assert n == len(ROUTES), "ROUTES is out of step with VISREP_ROUTE_COUNT"
-    return dict(zip(ROUTES, list(buf)))
+    assert n == len(names), "ROUTES + CONVNEXT_ROUTES are out of step with VISREP_ROUTE_COUNT"
+    return dict(zip(names, list(buf)))
 
 
 def last_error() -> str:

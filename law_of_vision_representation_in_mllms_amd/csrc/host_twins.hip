@@ -440,3 +440,82 @@ extern "C" int visrep_pck_count_cpu(const float* xy, const float* kps1, const fl
     }
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------ ConvNeXt twins
+// HF ConvNextLayer.forward (dwconv -> channels-last LayerNorm) and ConvNextStage.downsampling_layer (LayerNorm -> 2x2 stride-2 convolution),
+// restated on the device kernels' contract: bf16 storage in and out (HOST pointers), fp32 fmaf chains in the device order.
+namespace {
+inline float bf16_to_f32(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
+inline uint16_t f32_to_bf16(float f) {                              // round to nearest even; NaN stays NaN
+    uint32_t u; memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+}  // namespace
+
+extern "C" int visrep_dwconv7x7_stats_cpu(const void* x_, int ldx, const float* wt, const float* bias, void* y_, int ldy, float* rt, int B, int H, int W,
+                                          int C, float eps, int threads) {
+    if (!x_ || !wt || !bias || !y_ || !rt) return visrep_set_error(VISREP_ERR_ARG, "dwconv7x7_cpu: null pointer");
+    if (x_ == y_) return visrep_set_error(VISREP_ERR_ARG, "dwconv7x7_cpu: y must not alias x");
+    if (C <= 0 || C % 64) return visrep_set_error(VISREP_ERR_SHAPE, "dwconv7x7_cpu: C must be a positive multiple of 64");
+    if (B < 0 || H < 1 || W < 1) return visrep_set_error(VISREP_ERR_SHAPE, "dwconv7x7_cpu: need B >= 0, H >= 1, W >= 1");
+    if (ldx % 8 || ldy % 8 || ldx < C || ldy < C) return visrep_set_error(VISREP_ERR_SHAPE, "dwconv7x7_cpu: ldx / ldy must be multiples of 8 and >= C");
+    const uint16_t* x = (const uint16_t*)x_;
+    uint16_t* y = (uint16_t*)y_;
+    parallel_for((long)B * H, threads, [&](long item) {
+        const long b = item / H;
+        const int oy = (int)(item - b * H);
+        for (int ox = 0; ox < W; ++ox) {
+            const size_t r = ((size_t)b * H + oy) * W + ox;
+            double s1 = 0.0, s2 = 0.0;
+            for (int c = 0; c < C; ++c) {
+                float acc = bias[c];
+                for (int ky = 0; ky < 7; ++ky) {
+                    const int iy = oy + ky - 3;
+                    if (iy < 0 || iy >= H) continue;                  // a zero-padded tap adds fmaf(0, w, acc) = acc
+                    for (int kx = 0; kx < 7; ++kx) {
+                        const int ix = ox + kx - 3;
+                        if (ix < 0 || ix >= W) continue;
+                        acc = fmaf(bf16_to_f32(x[(((size_t)b * H + iy) * W + ix) * ldx + c]), wt[(size_t)(ky * 7 + kx) * C + c], acc);
+                    }
+                }
+                const uint16_t h = f32_to_bf16(acc);
+                y[r * ldy + c] = h;
+                const double v = bf16_to_f32(h);                       // statistics of the ROUNDED outputs: what the GEMM reads
+                s1 += v; s2 += v * v;
+            }
+            const double mean = s1 / C, var = std::max(s2 / C - mean * mean, 0.0);
+            const double rstd = 1.0 / sqrt(var + (double)eps);
+            rt[2 * r] = (float)rstd;
+            rt[2 * r + 1] = (float)(-mean * rstd);
+        }
+    });
+    return 0;
+}
+
+extern "C" int visrep_ln_space_to_depth2_cpu(const void* x_, int ldx, const float* gamma, const float* beta, void* out_, int ldo, int B, int H, int W,
+                                             int C, float eps, int threads) {
+    if (!x_ || !gamma || !beta || !out_) return visrep_set_error(VISREP_ERR_ARG, "ln_space_to_depth2_cpu: null pointer");
+    if (x_ == out_) return visrep_set_error(VISREP_ERR_ARG, "ln_space_to_depth2_cpu: out must not alias x");
+    if (C <= 0 || C % 8 || C > 4096) return visrep_set_error(VISREP_ERR_SHAPE, "ln_space_to_depth2_cpu: C must be a multiple of 8, at most 4096");
+    if (B < 0 || H < 2 || W < 2 || (H & 1) || (W & 1)) return visrep_set_error(VISREP_ERR_SHAPE, "ln_space_to_depth2_cpu: H and W must be even and >= 2");
+    if (ldx % 8 || ldo % 8 || ldx < C || (long)ldo < 4L * C) return visrep_set_error(VISREP_ERR_SHAPE, "ln_space_to_depth2_cpu: ldx % 8, ldo % 8, ldx >= C and ldo >= 4 C required");
+    const uint16_t* x = (const uint16_t*)x_;
+    uint16_t* out = (uint16_t*)out_;
+    parallel_for((long)B * H, threads, [&](long item) {
+        const long b = item / H;
+        const int py = (int)(item - b * H);
+        for (int px = 0; px < W; ++px) {
+            const uint16_t* xr = x + (((size_t)b * H + py) * W + px) * ldx;
+            double mean = 0.0;
+            for (int c = 0; c < C; ++c) mean += bf16_to_f32(xr[c]);
+            mean /= C;
+            double var = 0.0;
+            for (int c = 0; c < C; ++c) { const double t = bf16_to_f32(xr[c]) - mean; var += t * t; }
+            const float rstd = (float)(1.0 / sqrt(var / C + (double)eps)), mu = (float)mean;
+            uint16_t* o = out + (((size_t)b * (H / 2) + py / 2) * (W / 2) + px / 2) * ldo + (size_t)((py & 1) * 2 + (px & 1)) * C;
+            for (int c = 0; c < C; ++c) o[c] = f32_to_bf16((bf16_to_f32(xr[c]) - mu) * rstd * gamma[c] + beta[c]);
+        }
+    });
+    return 0;
+}

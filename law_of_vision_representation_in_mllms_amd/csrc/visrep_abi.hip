@@ -2,6 +2,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <mutex>
 
 #include <cstdlib>
@@ -491,5 +492,90 @@ extern "C" int visrep_vit_forward(const visrep_vit_config* c, const visrep_vit_w
         rt_ready = fold_next;
         VR_TRY(visrep_gemm_dispatch(f, s));
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ ConvNeXt forward
+namespace {
+struct CnWs { size_t x, y, h, rt, part, total; };
+inline int cn_wp(int c) { return (c + 127) / 128 * 128; }
+CnWs cn_layout(const visrep_convnext_config* c, int B) {
+    CnWs w;
+    size_t ex = 0, ey = 0, eh = 0, ep = 0, side = (size_t)c->image_size / 4;
+    const size_t M0 = up((size_t)B * side * side, 256);
+    eh = M0 * c->kpad;                                               // the stem's im2col columns alias the pwconv1 output
+    for (int s = 0; s < 4; ++s) {                                    // elements each buffer needs at its largest stage; rows padded to whole 256-row tiles
+        if (s) side /= 2;
+        const size_t M = up((size_t)B * side * side, 256), C = c->widths[s];
+        ex = std::max(ex, M * cn_wp((int)C));                        // residual stream [M_s, wp(s)]
+        ey = std::max(ey, M * std::max(C, s ? (size_t)4 * c->widths[s - 1] : C));   // dwconv output [M_s, C_s] / space-to-depth rows [M_s, 4 C_(s-1)]
+        eh = std::max(eh, M * 4 * C);                                // pwconv1 output [M_s, 4 C_s]
+        ep = std::max(ep, M * (C / 64));
+    }
+    size_t off = 0;
+    w.x = off;  off += up(ex * 2, 256);
+    w.y = off;  off += up(ey * 2, 256);
+    w.h = off;  off += up(eh * 2, 256);
+    w.rt = off; off += up((M0 + 8) * sizeof(float2), 256);
+    w.part = off; off += up(ep * sizeof(float2), 256);
+    w.total = off;
+    return w;
+}
+int cn_check(const visrep_convnext_config* c) {
+    if (c->image_size <= 0 || c->image_size % 32) return visrep_set_error(VISREP_ERR_SHAPE, "convnext: image_size must be a positive multiple of 32");
+    if (c->kpad < 48 || c->kpad % 64) return visrep_set_error(VISREP_ERR_SHAPE, "convnext: kpad must be a multiple of 64 (48 stem taps zero-padded)");
+    for (int s = 0; s < 4; ++s) {
+        if (c->widths[s] <= 0 || c->widths[s] % 64) return visrep_set_error(VISREP_ERR_SHAPE, "convnext: every stage width must be a multiple of 64");
+        if (c->depths[s] < 0) return visrep_set_error(VISREP_ERR_SHAPE, "convnext: negative depth");
+    }
+    if (c->widths[0] > 2048) return visrep_set_error(VISREP_ERR_SHAPE, "convnext: stem width above 2048 is not supported (visrep_layernorm)");
+    return 0;
+}
+}  // namespace
+
+extern "C" size_t visrep_convnext_workspace_bytes(const visrep_convnext_config* cfg, int B) {
+    if (!cfg || B <= 0 || cn_check(cfg)) return 0;
+    return cn_layout(cfg, B).total;
+}
+
+extern "C" int visrep_convnext_forward(const visrep_convnext_config* c, const visrep_convnext_weights* w, const void* pixels, int pixel_dtype,
+                                       void* hidden, int B, int n_stages, void* workspace, void* stream) {
+    if (!c || !w || !pixels || !hidden || !workspace || !w->blocks) return visrep_set_error(VISREP_ERR_ARG, "convnext_forward: null pointer");
+    if (B <= 0) return 0;
+    if (n_stages < 0 || n_stages > 4) return visrep_set_error(VISREP_ERR_ARG, "convnext_forward: n_stages must be 0 .. 4");
+    VR_TRY(cn_check(c));
+    hipStream_t s = (hipStream_t)stream;
+    const CnWs L = cn_layout(c, B);
+    char* base = (char*)workspace;
+    bf16_t* x = (bf16_t*)(base + L.x);
+    bf16_t* y = (bf16_t*)(base + L.y);
+    bf16_t* h = (bf16_t*)(base + L.h);
+    float2* rt = (float2*)(base + L.rt);
+    float2* part = (float2*)(base + L.part);
+    int side = c->image_size / 4, C = c->widths[0], Cp = cn_wp(C), M = B * side * side;
+    if (hipMemsetAsync(rt, 0, (up((size_t)M, 256) + 8) * sizeof(float2), s) != hipSuccess) return visrep_set_error(VISREP_ERR_LAUNCH, "convnext_forward: memset failed");
+    // ---- stem: conv(k = s = 4) as im2col + GEMM, then LayerNorm over the true width (the padded columns of x are and stay zero)
+    VR_TRY(visrep_im2col(pixels, pixel_dtype, h, B, c->image_size, c->image_size, 4, c->kpad, stream));
+    VR_TRY(visrep_gemm_bf16(h, c->kpad, w->stem_w, c->kpad, w->stem_b, x, Cp, M, Cp, c->kpad, VISREP_EPI_BIAS, 0, nullptr, nullptr, stream));
+    VR_TRY(visrep_layernorm(x, Cp, w->stem_ln_g, w->stem_ln_b, x, Cp, M, C, c->eps, stream));
+    const visrep_convnext_block* blk = w->blocks;
+    for (int st = 0; st < n_stages; ++st) {
+        if (st > 0) {                                                // LayerNorm + 2x2 stride-2 convolution: gather kernel + plain GEMM, x is rewritten
+            const int Ci = C;
+            if (!w->ds_ln_g[st] || !w->ds_ln_b[st] || !w->ds_w[st]) return visrep_set_error(VISREP_ERR_ARG, "convnext_forward: a downsampling layer's weights are missing");
+            VR_TRY(visrep_ln_space_to_depth2(x, Cp, w->ds_ln_g[st], w->ds_ln_b[st], y, 4 * Ci, B, side, side, Ci, c->eps, stream));
+            side /= 2; C = c->widths[st]; Cp = cn_wp(C); M = B * side * side;
+            VR_TRY(visrep_gemm_bf16(y, 4 * Ci, w->ds_w[st], 4 * Ci, w->ds_b[st], x, Cp, M, Cp, 4 * Ci, VISREP_EPI_BIAS, 0, nullptr, nullptr, stream));
+        }
+        for (int i = 0; i < c->depths[st]; ++i, ++blk) {
+            if (!blk->dw_w || !blk->dw_b || !blk->w1 || !blk->s1 || !blk->w2) return visrep_set_error(VISREP_ERR_ARG, "convnext_forward: a block's weights are missing");
+            VR_TRY(visrep_dwconv7x7_stats(x, Cp, blk->dw_w, blk->dw_b, y, C, part, rt, B, side, side, C, c->eps, stream));
+            VR_TRY(visrep_gemm_bf16_ln(y, C, blk->w1, C, blk->b1, rt, blk->s1, h, 4 * C, M, 4 * C, C, VISREP_EPI_ACT, VISREP_ACT_GELU_ERF, stream));
+            VR_TRY(visrep_gemm_bf16(h, 4 * C, blk->w2, 4 * C, blk->b2, x, Cp, M, Cp, 4 * C, VISREP_EPI_RESID, 0, x, blk->ls, stream));
+        }
+    }
+    // hidden is [B, side^2, C] without the padded columns
+    if (hipMemcpy2DAsync(hidden, (size_t)C * 2, x, (size_t)Cp * 2, (size_t)C * 2, (size_t)M, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return visrep_set_error(VISREP_ERR_LAUNCH, "convnext_forward: copy of the hidden state failed");
     return 0;
 }

@@ -716,3 +716,140 @@ def mhsa_prefix(qk: torch.Tensor, vt: torch.Tensor, vpre: torch.Tensor, B: int, 
                                     out.stride(0), B, T, prefix, H, 64, _lib.stream_ptr())
     _lib.check(rc, "visrep_mhsa_prefix_fwd")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ ConvNeXt
+class ConvNextEngine:
+    """One ConvNeXt tower on one GPU (visrep_convnext_forward): forward(pixels, n_stages) returns hidden_states[n_stages] of HF ConvNextModel as
+    bf16 token rows [B, H_s W_s, C_s] - index 0 = the stem output, 1 .. 4 = the stage outputs.  bf16 on the GPU only: there is no fp32 and no
+    host ConvNeXt engine, and asking for one is an error, never a fallback."""
+
+    def __init__(self, spec, weights: dict, device: Optional[torch.device] = None):
+        from . import convnext_weights as CW
+        if device is not None and torch.device(device).type == "cpu":
+            raise ValueError("ConvNeXt towers have no host engine (device='cpu'): only the bf16 HIP engine exists")
+        self.lib = _lib.require_gpu()
+        self.spec = spec
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.n_layers = 4                                  # the tower protocol's name for "last hidden-state index"
+        ensure_scratch(self.device)
+        self._keep = []
+
+        def dev(t):
+            if t is None:
+                return 0
+            x = t.detach().to(device=self.device).contiguous()
+            self._keep.append(x)
+            return x.data_ptr()
+
+        D = CW.device_layout(spec, weights)
+        nblk = sum(spec.depths)
+        self._blocks = (_lib.ConvNextBlock * nblk)()
+        self._w = _lib.ConvNextWeights()
+        for k in ("stem_w", "stem_b", "stem_ln_g", "stem_ln_b"):
+            setattr(self._w, k, dev(D[k]))
+        i = 0
+        for st, stage in enumerate(D["stages"]):
+            if len(stage["blocks"]) != spec.depths[st]:
+                raise ValueError(f"stage {st} has {len(stage['blocks'])} blocks, spec wants {spec.depths[st]}")
+            for k in ("ds_ln_g", "ds_ln_b", "ds_w", "ds_b"):
+                getattr(self._w, k)[st] = dev(stage[k])
+            for L in stage["blocks"]:
+                for k in ("dw_w", "dw_b", "w1", "b1", "s1", "w2", "b2", "ls"):
+                    setattr(self._blocks[i], k, dev(L[k]))
+                i += 1
+        self._w.blocks = C.cast(self._blocks, C.POINTER(_lib.ConvNextBlock))
+        self._cfg = _lib.ConvNextConfig(spec.image_size, 64, (C.c_int * 4)(*spec.depths), (C.c_int * 4)(*spec.hidden_sizes), float(spec.eps))
+        self._ws: Dict[int, torch.Tensor] = {}
+
+    def workspace(self, B: int) -> torch.Tensor:
+        ws = self._ws.get(B)
+        if ws is None:
+            nbytes = self.lib.visrep_convnext_workspace_bytes(C.byref(self._cfg), B)
+            if nbytes == 0:
+                raise RuntimeError(f"visrep_convnext_workspace_bytes refused the tower: {_lib.last_error()}")
+            if len(self._ws) > 4:
+                self._ws.clear()
+            ws = self._ws[B] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        return ws
+
+    @torch.no_grad()
+    def forward(self, pixels: torch.Tensor, n_stages: Optional[int] = None, out: Optional[torch.Tensor] = None, n_layers: Optional[int] = None) -> torch.Tensor:
+        s = self.spec
+        if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != s.image_size or pixels.shape[3] != s.image_size:
+            raise ValueError(f"Input image size {tuple(pixels.shape)} doesn't match tower ({s.image_size}*{s.image_size}).")
+        if n_stages is None:
+            n_stages = 4 if n_layers is None else n_layers
+        if not 0 <= n_stages <= 4:
+            raise ValueError("n_stages out of range (0 = stem output, 1 .. 4 = stage outputs)")
+        px = pixels.to(self.device)
+        if px.dtype not in (torch.float32, torch.bfloat16):
+            px = px.float()
+        px = px.contiguous()
+        B = px.shape[0]
+        if out is None:
+            out = torch.empty(B, s.grid(n_stages) ** 2, s.width(n_stages), dtype=torch.bfloat16, device=self.device)
+        ws = self.workspace(B)
+        with torch.cuda.device(self.device):
+            rc = self.lib.visrep_convnext_forward(C.byref(self._cfg), C.byref(self._w), _lib.ptr(px), _lib.F32 if px.dtype == torch.float32 else _lib.BF16,
+                                                  _lib.ptr(out), B, n_stages, _lib.ptr(ws), _lib.stream_ptr())
+        _lib.check(rc, "visrep_convnext_forward")
+        return out
+
+
+def make_convnext_engine(spec, weights: dict, device=None, precision: str = "bf16") -> ConvNextEngine:
+    """make_engine for ConvNeXt towers: bf16 on the GPU, and a ValueError that says so for anything else."""
+    if precision not in ("bf16", "bfloat16"):
+        raise ValueError(f"ConvNeXt towers run in bf16 only: there is no {precision} ConvNeXt engine (a full fp32 engine is out of scope)")
+    return ConvNextEngine(spec, weights, device)
+
+
+def dwconv7x7_stats(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, C: Optional[int] = None, eps: float = 1e-6):
+    """x [B, H, W, ldx] bf16 (the first C columns are the channels) -> (y [B, H, W, C] bf16, rt [B H W, 2] fp32) - visrep_dwconv7x7_stats."""
+    lib = _lib.require_gpu()
+    B, H, W, ldx = x.shape
+    C = ldx if C is None else C
+    rows = B * H * W
+    y = torch.empty(B, H, W, C, dtype=torch.bfloat16, device=x.device)
+    part = torch.empty(max(rows, 1) * max(C // 64, 1), 2, dtype=torch.float32, device=x.device)
+    rt = torch.zeros(_round_up(rows, 128) + 8, 2, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.visrep_dwconv7x7_stats(_lib.ptr(x), ldx, _lib.ptr(wt), _lib.ptr(bias), _lib.ptr(y), C, _lib.ptr(part), _lib.ptr(rt), B, H, W, C,
+                                              float(eps), _lib.stream_ptr()), "visrep_dwconv7x7_stats")
+    return y, rt[:rows]
+
+
+def ln_space_to_depth2(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, C: Optional[int] = None, eps: float = 1e-6) -> torch.Tensor:
+    """x [B, H, W, ldx] bf16 -> [B (H/2) (W/2), 4 C] bf16 - visrep_ln_space_to_depth2."""
+    lib = _lib.require_gpu()
+    B, H, W, ldx = x.shape
+    C = ldx if C is None else C
+    out = torch.empty(B * (H // 2) * (W // 2), 4 * C, dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.visrep_ln_space_to_depth2(_lib.ptr(x), ldx, _lib.ptr(g), _lib.ptr(b), _lib.ptr(out), 4 * C, B, H, W, C, float(eps),
+                                                 _lib.stream_ptr()), "visrep_ln_space_to_depth2")
+    return out
+
+
+def dwconv7x7_stats_cpu(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, C: Optional[int] = None, eps: float = 1e-6, threads: int = 0):
+    """Host twin of dwconv7x7_stats (HOST bf16 tensors; no GPU needed)."""
+    lib = _lib.load()
+    B, H, W, ldx = x.shape
+    C = ldx if C is None else C
+    x, wt, bias = x.contiguous(), wt.float().contiguous(), bias.float().contiguous()
+    y = torch.empty(B, H, W, C, dtype=torch.bfloat16)
+    rt = torch.zeros(B * H * W, 2, dtype=torch.float32)
+    _lib.check(lib.visrep_dwconv7x7_stats_cpu(_lib.ptr(x), ldx, _lib.ptr(wt), _lib.ptr(bias), _lib.ptr(y), C, _lib.ptr(rt), B, H, W, C, float(eps), threads),
+               "visrep_dwconv7x7_stats_cpu")
+    return y, rt
+
+
+def ln_space_to_depth2_cpu(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, C: Optional[int] = None, eps: float = 1e-6, threads: int = 0) -> torch.Tensor:
+    lib = _lib.load()
+    B, H, W, ldx = x.shape
+    C = ldx if C is None else C
+    x, g, b = x.contiguous(), g.float().contiguous(), b.float().contiguous()
+    out = torch.empty(B * (H // 2) * (W // 2), 4 * C, dtype=torch.bfloat16)
+    _lib.check(lib.visrep_ln_space_to_depth2_cpu(_lib.ptr(x), ldx, _lib.ptr(g), _lib.ptr(b), _lib.ptr(out), 4 * C, B, H, W, C, float(eps), threads),
+               "visrep_ln_space_to_depth2_cpu")
+    return out

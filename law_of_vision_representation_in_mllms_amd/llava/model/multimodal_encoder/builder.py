@@ -9,6 +9,7 @@ towers are pre-extracted features and have no module.
 import os
 
 from .clip_encoder import CLIPVisionTower
+from .convnext_encoder import ConvNextVisionTower
 from .diffLVLM.diffusion_encoder import DiffVisionTower
 from .dinov2_encoder import DinoV2VisionTower
 from .internvit_encoder import InternViTVisionTower
@@ -44,6 +45,11 @@ def build_siglip_vision_tower(vision_tower_cfg, **kwargs):
 def build_internvit_vision_tower(vision_tower_cfg, **kwargs):
     """InternViT (the InternVL vision tower).  Not a reference registry entry: add the id to llava_arch.build_function_mapping."""
     return _make(InternViTVisionTower, vision_tower_cfg, kwargs)
+
+
+def build_convnext_vision_tower(vision_tower_cfg, **kwargs):
+    """ConvNeXt (HF ConvNextModel, OpenCLIP's convnext_* trunks).  Not a reference registry entry: add the id to llava_arch.build_function_mapping."""
+    return _make(ConvNextVisionTower, vision_tower_cfg, kwargs)
 
 
 def build_diffusion_vision_tower(vision_tower_cfg, **kwargs):
