@@ -101,7 +101,12 @@ enum {
     VISREP_ROUTE_DWCONV_8 = 20,      /* dwconv7x7_stats_tile<8, 8>: the same on 8 x 8 tiles (small or ragged maps) */
     VISREP_ROUTE_DWCONV_FINALIZE = 21, /* the statistics finalize behind either (ln_stats_finalize_rows, or its odd-slot form) */
     VISREP_ROUTE_LN_S2D = 22,        /* ln_space_to_depth2_rows (visrep_ln_space_to_depth2) */
-    VISREP_ROUTE_COUNT = 23
+    /* SAM ViT towers (attention_relpos.hip).  New ids only, as above */
+    VISREP_ROUTE_ATTN_RELPOS = 23,   /* attn_fwd_relpos (visrep_mhsa_relpos_fwd) */
+    VISREP_ROUTE_RELPOS_TABLES = 24, /* relpos_tables_rows (visrep_relpos_tables) */
+    VISREP_ROUTE_SAM_PARTITION = 25, /* sam_window_partition_qk + _vt (one count per visrep_sam_window_partition), sam_window_unpartition_rows */
+    VISREP_ROUTE_SAM_NECK = 26,      /* the neck of visrep_sam_forward (one count per forward that reaches it: GEMM, LayerNorm, 3x3 convolution, LayerNorm) */
+    VISREP_ROUTE_COUNT = 27
 };
 int visrep_debug_routes(long* out, int reset);
 /* Matrix-pipe ceiling of THIS device under THIS process' conditions: `iters` bursts of 32 dependent-free v_mfma_f32_16x16x32_bf16 per wave,
@@ -405,6 +410,86 @@ typedef struct {
 size_t visrep_convnext_workspace_bytes(const visrep_convnext_config* cfg, int B);
 int visrep_convnext_forward(const visrep_convnext_config* cfg, const visrep_convnext_weights* w, const void* pixels, int pixel_dtype, void* hidden,
                             int B, int n_stages, void* workspace, void* stream);
+
+/* ---- SAM ViT towers (HF SamVisionModel / the Segment Anything image encoder, ViTDet style): attention whose logits carry the decomposed
+ * relative-position term, over 14 x 14 windows of the patch grid in most layers and over the whole grid in a few.
+ *
+ * visrep_mhsa_relpos_fwd replaces SamVisionAttention.forward from `attn_weights = (query * self.scale) @ key.transpose(-2, -1)` through
+ * add_decomposed_rel_pos's `attn + rel_h[:, :, :, :, None] + rel_w[:, :, :, None, :]`, the fp32 softmax and `attn_probs @ value`:
+ *   out[g, q, h, :] = softmax_k( scale * Q[g,q,h,:] . K[g,k,h,:] + rel_h[g,h,q, k / S] + rel_w[g,h,q, k % S] ) V[g,k,h,:]
+ * over NB independent S x S token grids (T = S S tokens each; NB = batch x windows, or the batch for a global layer).  qk [NB T, ldqk] bf16
+ * (Q | K, head-major, K at column H 64), vt [H 64, ldvt] as VISREP_EPI_VT writes it over the NB T key rows (ldvt >= round_up(NB T, 64),
+ * % 64 == 0, columns that belong to no key finite), out [NB T, ldo] bf16; rel_h, rel_w: fp32 [NB, H, T, S], taken as given (fp32 on purpose:
+ * a bf16 table would put 2^-9 |bias| straight into the logits).  scale > 0 only: Q is the UNSCALED query (the position term uses it), so
+ * there is no pre-scaled-Q form.  Rounding sequence per logit, all fp32: s = the MFMA's q.k; b = rel_h + rel_w; t = fma(s, scale log2 e,
+ * b log2 e); p = exp2(t - m) with m the running reference (first tile's row maximum, moved when a later tile's exceeds it by more than 8);
+ * the row sum adds the fp32 p, P.V takes p rounded to bf16, one bf16 rounding of O / l.  2 <= S <= 64, head_dim 64.  No scratch memory.
+ * Pointers: none null; qk and vt 16-byte, out 8-byte, rel_h and rel_w 4-byte aligned; ldqk % 8, ldvt % 64, ldo % 4 - anything else is
+ * refused (VISREP_ERR_ARG / VISREP_ERR_SHAPE) before any launch.  Nothing outside [row, h 64 .. + 64) of the NB T output rows is written;
+ * K rows past the last key row, qk columns outside the heads and table entries of other (grid, head)s are never read.
+ * Non-finite data, in the terms of the attention contract above: key tiles are the global 64-key blocks, so a key outside the grid is not
+ * skipped - its score is overwritten with -inf and it enters P.V with weight exactly 0.  A NaN / Inf in the Q, K or tables of one grid never
+ * reaches another grid (a table row belongs to one query); a NaN / Inf in grid g's V reaches the grids that share a key tile with the bad
+ * key (g - 1 and / or g + 1: 0 * NaN) and no other.  With finite data every grid is bitwise independent of its neighbours' contents; its
+ * result depends on its own data and on g T % 64 (where the tile boundaries fall inside it).
+ *
+ * visrep_relpos_tables replaces get_rel_pos + the two einsums of get_decomposed_rel_pos ("bhwc,hkc->bhwk", "bhwc,wkc->bhwk"):
+ *   rel_h[g, h, q, kh] = sum_c Q[g T + q, h 64 + c] * Rh[q / S - kh + S - 1, c],   rel_w[g, h, q, kw] likewise with Rw and q % S - kw,
+ * Q = the first H 64 columns of the rows of qk (bf16, ldqk % 8 == 0, 16-byte aligned), Rh / Rw fp32 [2 S - 1, 64] (16-byte aligned; a table
+ * of another length is refused by the weight packer).  Summation order: ONE fp32 fmaf chain over c = 0, 1, .. 63
+ * starting from +0 - the host twin runs the same chain and equals the kernel bit for bit.
+ *
+ * visrep_sam_window_partition / _unpartition replace window_partition / window_unpartition of SamVisionLayer together with the zero
+ * padding in front of the QKV projection: the PROJECTED tokens are gathered.  Window row r = ((b nw + wy) nw + wx) w w + iy w + ix holds map
+ * token (b, wy w + iy, wx w + ix), nw = ceil(g / w); a position past the map's bottom or right edge holds bf16(bias) - what qkv(0) is: bias
+ * [3 d] fp32 is the RAW qkv bias (q | k | v), not the folded one.  qk [B g g, ldqk] -> qk_win [B nw nw w w, ldqw] (2 d columns), vt
+ * [d, ldvt] -> vt_win [d, ldvw] (column perm16(row) on both sides).  unpartition copies the d columns of every map token's window row and
+ * drops the pad rows.  d % 8 == 0; row pointers 16-byte aligned.
+ * The _cpu forms are host twins on HOST pointers: plain C++ fp32 (float64 for the softmax sums), the same contract. */
+int visrep_mhsa_relpos_fwd(const void* qk, int ldqk, const void* vt, int ldvt, const float* rel_h, const float* rel_w, void* out, int ldo, int NB,
+                           int S, int H, int head_dim, float scale, void* stream);
+int visrep_relpos_tables(const void* qk, int ldqk, const float* Rh, const float* Rw, float* rel_h, float* rel_w, int NB, int S, int H, int head_dim,
+                         void* stream);
+int visrep_sam_window_partition(const void* qk, int ldqk, const void* vt, int ldvt, const float* bias, void* qk_win, int ldqw, void* vt_win, int ldvw,
+                                int B, int g, int window, int d, void* stream);
+int visrep_sam_window_unpartition(const void* win, int ldw, void* out, int ldo, int B, int g, int window, int d, void* stream);
+/* Host twins.  visrep_mhsa_relpos_cpu: q, k, v [NB T, ld*] fp32 ROW-major (v is not transposed), out fp32; the softmax of
+ * scale q.k + rel_h + rel_w in fp32 logits and float64 sums, no bf16 rounding anywhere. */
+int visrep_mhsa_relpos_cpu(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel_h, const float* rel_w, float* out,
+                           int ldo, int NB, int S, int H, int head_dim, float scale, int threads);
+int visrep_relpos_tables_cpu(const void* qk, int ldqk, const float* Rh, const float* Rw, float* rel_h, float* rel_w, int NB, int S, int H, int head_dim,
+                             int threads);
+/* Composed tower: state `n_state` of HF SamVisionModel(output_hidden_states=True) as token rows - 0 = patch embedding + absolute positions,
+ * 1 .. layers = the block outputs [B, g g, d], layers + 1 = the neck output [B, g g, out_ch] (conv1x1 -> LayerNorm over channels -> conv3x3
+ * -> LayerNorm over channels).  A block is x + attn(LN1(x)) then x + fc2(GELU(fc1(LN2(x)))); layer l attends over the whole grid when bit l
+ * of global_mask is set, over window x window windows otherwise.  Composition: visrep_im2col + GEMM (EPI_PATCH); folded-LayerNorm Q | K and
+ * V GEMMs over the UNPADDED tokens; windowed layers: visrep_sam_window_partition (pad rows = the raw bias bqkv_raw); visrep_relpos_tables +
+ * visrep_mhsa_relpos_fwd in chunks of images such that each table stays within its 64 MiB of the workspace (as many images as fit, at
+ * least one; a chunk is a range of grids of the same buffers, so the result does not depend on the chunk size); unpartition; the residual GEMMs with LayerNorm
+ * statistics; fc1 with exact GELU; fc2.  The neck: plain
+ * GEMM, visrep_layernorm, visrep_conv3x3_bf16, visrep_layernorm.  wqkv / bqkv / sqkv and w1 / b1 / s1 are the folded forms (as the ViT
+ * blocks'); rel_h / rel_w fp32 [2 S - 1, 64] with S = window or g.  d, mlp % 128 == 0, out_ch % 64 == 0, heads 64 wide, kpad % 64 == 0. */
+typedef struct {
+    int image_size, patch, d, layers, heads, mlp, window, out_ch, kpad;
+    unsigned long long global_mask;
+    float eps, neck_eps;
+} visrep_sam_config;
+typedef struct {
+    const void* wqkv; const float *bqkv, *sqkv, *bqkv_raw, *rel_h, *rel_w; const void* wo; const float* bo;
+    const void* w1; const float *b1, *s1; const void* w2; const float* b2;
+} visrep_sam_layer;
+typedef struct {
+    const void* patch_w; const float *patch_b, *pos;
+    const void* neck_w1; const float *neck_ln1_g, *neck_ln1_b; const void* neck_w2; const float *neck_ln2_g, *neck_ln2_b;
+    const visrep_sam_layer* layers;         /* HOST array of `layers` entries */
+} visrep_sam_weights;
+size_t visrep_sam_workspace_bytes(const visrep_sam_config* cfg, int B);
+/* Tests: the per-table budget (bytes) the calling thread's visrep_sam_forward sizes its image chunks to, so that a small tower reaches the
+ * chunked path; 0 = the default (64 MiB, also the most: the workspace holds that much).  Returns the previous value.  Results do not depend
+ * on it. */
+size_t visrep_debug_sam_table_bytes(size_t bytes);
+int visrep_sam_forward(const visrep_sam_config* cfg, const visrep_sam_weights* w, const void* pixels, int pixel_dtype, void* hidden, int B,
+                       int n_state, void* workspace, void* stream);
 
 /* ---- reference-precision (fp32) tower path.  The reference builds the C-score CLIP / OpenCLIP / DINOv2 towers with no dtype cast and
  * fp32 pixels (C_score/extract_feature.py:36-45,49-50,80-87): every tensor and accumulation here is fp32 (v_mfma_f32_32x32x2_f32 = an

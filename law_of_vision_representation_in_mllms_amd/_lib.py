@@ -50,6 +50,20 @@ class ConvNextWeights(C.Structure):
         (n, C.c_void_p * 4) for n in ("ds_ln_g", "ds_ln_b", "ds_w", "ds_b")] + [("blocks", C.POINTER(ConvNextBlock))]
 
 
+class SamConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("image_size", "patch", "d", "layers", "heads", "mlp", "window", "out_ch", "kpad")] + [
+        ("global_mask", C.c_ulonglong), ("eps", C.c_float), ("neck_eps", C.c_float)]
+
+
+class SamLayer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("wqkv", "bqkv", "sqkv", "bqkv_raw", "rel_h", "rel_w", "wo", "bo", "w1", "b1", "s1", "w2", "b2")]
+
+
+class SamWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("patch_w", "patch_b", "pos", "neck_w1", "neck_ln1_g", "neck_ln1_b", "neck_w2", "neck_ln2_g", "neck_ln2_b")] + [
+        ("layers", C.POINTER(SamLayer))]
+
+
 class JpegInfo(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("ncomp", C.c_int), ("hs", C.c_int * 3), ("vs", C.c_int * 3), ("hmax", C.c_int),
                 ("vmax", C.c_int), ("mcus_w", C.c_int), ("mcus_h", C.c_int), ("blocks_w", C.c_int * 3), ("blocks_h", C.c_int * 3),
@@ -95,6 +109,15 @@ SIGNATURES = {
     "visrep_ln_space_to_depth2_cpu": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i]),
     "visrep_convnext_workspace_bytes": (_sz, [C.POINTER(ConvNextConfig), _i]),
     "visrep_convnext_forward": (_i, [C.POINTER(ConvNextConfig), C.POINTER(ConvNextWeights), _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "visrep_mhsa_relpos_fwd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "visrep_relpos_tables": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "visrep_sam_window_partition": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "visrep_sam_window_unpartition": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "visrep_mhsa_relpos_cpu": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i]),
+    "visrep_relpos_tables_cpu": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "visrep_sam_workspace_bytes": (_sz, [C.POINTER(SamConfig), _i]),
+    "visrep_debug_sam_table_bytes": (_sz, [_sz]),
+    "visrep_sam_forward": (_i, [C.POINTER(SamConfig), C.POINTER(SamWeights), _vp, _i, _vp, _i, _i, _vp, _vp]),
     "visrep_gemm_bf16_gated": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "visrep_swiglu": (_i, [_vp, _i, _vp, _i, _l, _i, _vp]),
     "visrep_swiglu_f32": (_i, [_vp, _i, _vp, _i, _l, _i, _vp]),
@@ -222,6 +245,10 @@ ROUTES = ("gemm_256", "gemm_128", "gemm_tail", "splitk", "conv_256", "conv_128",
 CONVNEXT_ROUTES = ("dwconv_16", "dwconv_8", "dwconv_finalize", "ln_s2d")
 
 
+# SAM ViT launches (ids 23 .. 26), kept apart for the same reason: routes() keeps returning ids 0 .. 22, sam_routes() returns these.
+SAM_ROUTES = ("attn_relpos", "relpos_tables", "sam_partition", "sam_neck")
+
+
 def xcd_balance() -> dict:
     """{"on": bool, "rel": [8 floats: smoothed time per round of tiles of each XCD relative to the mean], "updates": measurements folded in}
     of the current device's XCD-weighted tile split (visrep_debug_xcd_balance)."""
@@ -231,13 +258,24 @@ def xcd_balance() -> dict:
     return {"on": bool(on), "rel": [round(float(v), 4) for v in rel], "updates": int(upd.value)}
 
 
-def routes(reset: bool = False) -> dict:
-    """This thread's launch counters per kernel family (visrep_debug_routes): {name: count}."""
-    names = ROUTES + CONVNEXT_ROUTES
+def _route_counters(reset: bool) -> list:
+    names = ROUTES + CONVNEXT_ROUTES + SAM_ROUTES
     buf = (C.c_long * len(names))()
     n = load().visrep_debug_routes(buf, int(reset))
-    assert n == len(names), "ROUTES + CONVNEXT_ROUTES are out of step with VISREP_ROUTE_COUNT"
-    return dict(zip(names, list(buf)))
+    assert n == len(names), "ROUTES + CONVNEXT_ROUTES + SAM_ROUTES are out of step with VISREP_ROUTE_COUNT"
+    return list(buf)
+
+
+def routes(reset: bool = False) -> dict:
+    """This thread's launch counters per kernel family (visrep_debug_routes): {name: count} of ROUTES + CONVNEXT_ROUTES.  reset clears every
+    counter, those of sam_routes() included."""
+    names = ROUTES + CONVNEXT_ROUTES
+    return dict(zip(names, _route_counters(reset)))
+
+
+def sam_routes(reset: bool = False) -> dict:
+    """The counters of the SAM tower's launches ({name: count} of SAM_ROUTES); reset as for routes()."""
+    return dict(zip(SAM_ROUTES, _route_counters(reset)[len(ROUTES) + len(CONVNEXT_ROUTES):]))
 
 
 def last_error() -> str:

@@ -519,3 +519,69 @@ extern "C" int visrep_ln_space_to_depth2_cpu(const void* x_, int ldx, const floa
     });
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------ SAM twins
+// SamVisionAttention's decomposed relative-position term and the attention that consumes it (visrep_relpos_tables / visrep_mhsa_relpos_fwd),
+// restated in plain C++: the tables as the device's single fmaf chain over c = 0 .. 63 (bit-equal), the attention in fp32 logits with
+// float64 sums and no bf16 rounding (a statement of the contract, not of the kernel's roundings).
+extern "C" int visrep_relpos_tables_cpu(const void* qk_, int ldqk, const float* Rh, const float* Rw, float* rel_h, float* rel_w, int NB, int S, int H,
+                                        int head_dim, int threads) {
+    if (head_dim != 64) return visrep_set_error(VISREP_ERR_SHAPE, "relpos_tables_cpu: only head_dim 64 is implemented");
+    if (S < 2 || S > 64) return visrep_set_error(VISREP_ERR_SHAPE, "relpos_tables_cpu: the grid side S must be 2 .. 64");
+    if (!qk_ || !Rh || !Rw || !rel_h || !rel_w) return visrep_set_error(VISREP_ERR_ARG, "relpos_tables_cpu: null pointer");
+    if (NB <= 0 || H <= 0) return visrep_set_error(VISREP_ERR_SHAPE, "relpos_tables_cpu: empty problem");
+    if ((ldqk % 8) || ldqk < H * 64) return visrep_set_error(VISREP_ERR_SHAPE, "relpos_tables_cpu: ldqk % 8 == 0 and >= H 64");
+    const uint16_t* qk = (const uint16_t*)qk_;
+    const int T = S * S;
+    parallel_for((long)NB * H * T, threads, [&](long row) {
+        const int qi = (int)(row % T), h = (int)((row / T) % H);
+        const long g = row / T / H;
+        const int qh = qi / S, qw = qi % S;
+        const uint16_t* qp = qk + ((size_t)g * T + qi) * ldqk + h * 64;
+        for (int j = 0; j < 2 * S; ++j) {
+            const bool isw = j >= S;
+            const int kx = isw ? j - S : j;
+            const float* R = (isw ? Rw : Rh) + (size_t)((isw ? qw : qh) - kx + S - 1) * 64;
+            float acc = 0.f;
+            for (int c = 0; c < 64; ++c) acc = fmaf(bf16_to_f32(qp[c]), R[c], acc);
+            (isw ? rel_w : rel_h)[row * S + kx] = acc;
+        }
+    });
+    return 0;
+}
+
+extern "C" int visrep_mhsa_relpos_cpu(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel_h, const float* rel_w,
+                                      float* out, int ldo, int NB, int S, int H, int head_dim, float scale, int threads) {
+    if (head_dim != 64) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_relpos_cpu: only head_dim 64 is implemented");
+    if (S < 2 || S > 64) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_relpos_cpu: the grid side S must be 2 .. 64");
+    if (!q || !k || !v || !rel_h || !rel_w || !out) return visrep_set_error(VISREP_ERR_ARG, "mhsa_relpos_cpu: null pointer");
+    if (NB <= 0 || H <= 0) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_relpos_cpu: empty problem");
+    if (!(scale > 0.f)) return visrep_set_error(VISREP_ERR_ARG, "mhsa_relpos_cpu: scale must be > 0");
+    if (ldq < H * 64 || ldk < H * 64 || ldv < H * 64 || ldo < H * 64) return visrep_set_error(VISREP_ERR_SHAPE, "mhsa_relpos_cpu: leading dimensions must cover H 64");
+    const int T = S * S;
+    parallel_for((long)NB * H * T, threads, [&](long row) {
+        const int qi = (int)(row % T), h = (int)((row / T) % H);
+        const long g = row / T / H;
+        const float* qp = q + ((size_t)g * T + qi) * ldq + h * 64;
+        const float *bh = rel_h + row * S, *bw = rel_w + row * S;
+        std::vector<float> t(T);
+        float m = -INFINITY;
+        for (int kk = 0; kk < T; ++kk) {
+            const float* kp = k + ((size_t)g * T + kk) * ldk + h * 64;
+            float dot = 0.f;
+            for (int c = 0; c < 64; ++c) dot = fmaf(qp[c], kp[c], dot);
+            t[kk] = fmaf(dot, scale, bh[kk / S] + bw[kk % S]);
+            m = std::max(m, t[kk]);
+        }
+        double l = 0.0, o[64] = {};
+        for (int kk = 0; kk < T; ++kk) {
+            const double p = exp((double)t[kk] - (double)m);
+            const float* vp = v + ((size_t)g * T + kk) * ldv + h * 64;
+            l += p;
+            for (int c = 0; c < 64; ++c) o[c] += p * vp[c];
+        }
+        float* op = out + ((size_t)g * T + qi) * ldo + h * 64;
+        for (int c = 0; c < 64; ++c) op[c] = (float)(o[c] / l);
+    });
+    return 0;
+}

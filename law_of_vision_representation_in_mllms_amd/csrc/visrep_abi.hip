@@ -579,3 +579,158 @@ extern "C" int visrep_convnext_forward(const visrep_convnext_config* c, const vi
         return visrep_set_error(VISREP_ERR_LAUNCH, "convnext_forward: copy of the hidden state failed");
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------ SAM ViT forward
+namespace {
+constexpr size_t SAM_TABLE_BYTES = (size_t)64 << 20;             // per table (rel_h, rel_w): the image chunk of a layer's attention is sized to it
+thread_local size_t t_sam_table_bytes = SAM_TABLE_BYTES;         // visrep_debug_sam_table_bytes
+struct SamWs { size_t x, h, ow, qk, vt, qkw, vtw, mlp, rt, part, tab, neck, total; int ldvt, ldvw, nw; long Mw; };
+SamWs sam_layout(const visrep_sam_config* c, int B) {
+    SamWs w;
+    const int g = c->image_size / c->patch, d = c->d;
+    const size_t M = (size_t)B * g * g, Mp = up(M, 256);
+    w.nw = (g + c->window - 1) / c->window;
+    w.Mw = (long)B * w.nw * w.nw * c->window * c->window;
+    const size_t Mwp = up((size_t)w.Mw, 256);
+    w.ldvt = (int)(up(M, 64) + 64);
+    w.ldvw = (int)(up((size_t)w.Mw, 64) + 64);
+    size_t off = 0;
+    w.x = off;   off += up(Mp * d * 2, 256);                        // residual stream
+    w.h = off;   off += up(Mp * d * 2, 256);                        // attention output, map rows
+    w.ow = off;  off += up(Mwp * d * 2, 256);                       // attention output of a windowed layer, window rows
+    w.qk = off;  off += up(Mp * 2 * d * 2, 256);
+    w.vt = off;  off += up((size_t)d * w.ldvt * 2, 256);
+    w.qkw = off; off += up(Mwp * 2 * d * 2, 256);                   // windowed Q | K
+    w.vtw = off; off += up((size_t)d * w.ldvw * 2, 256);
+    const size_t mlp_b = Mp * c->mlp * 2, cols_b = Mp * c->kpad * 2;
+    w.mlp = off; off += up(std::max(mlp_b, cols_b), 256);
+    w.rt = off;  off += up((Mp + 8) * sizeof(float2), 256);
+    w.part = off; off += up(Mp * (d / 64 + 1) * sizeof(float2), 256);
+    w.tab = off; off += 2 * SAM_TABLE_BYTES;
+    w.neck = off; off += up(2 * Mp * c->out_ch * 2, 256);
+    w.total = off;
+    return w;
+}
+int sam_check(const visrep_sam_config* c) {
+    if (c->image_size <= 0 || c->patch <= 0 || c->image_size % c->patch) return visrep_set_error(VISREP_ERR_SHAPE, "sam: image_size must be a positive multiple of patch");
+    const int g = c->image_size / c->patch;
+    if (c->heads <= 0 || c->d != c->heads * 64) return visrep_set_error(VISREP_ERR_SHAPE, "sam: heads must be 64 wide (d = heads * 64)");
+    if (c->d % 128 || c->mlp % 128 || c->kpad % 64 || c->kpad < 3 * c->patch * c->patch) return visrep_set_error(VISREP_ERR_SHAPE, "sam: d, mlp % 128 and kpad % 64 (>= 3 patch^2) required");
+    if (c->out_ch <= 0 || c->out_ch % 64 || c->out_ch > 2048) return visrep_set_error(VISREP_ERR_SHAPE, "sam: out_ch must be a multiple of 64, at most 2048");
+    if (c->layers < 0 || c->layers > 64) return visrep_set_error(VISREP_ERR_SHAPE, "sam: at most 64 layers (global_mask)");
+    if (g < 2 || g > 64) return visrep_set_error(VISREP_ERR_SHAPE, "sam: the patch grid side must be 2 .. 64 (global attention)");
+    if (c->window < 2 || c->window > 64) return visrep_set_error(VISREP_ERR_SHAPE, "sam: window must be 2 .. 64");
+    return 0;
+}
+}  // namespace
+
+extern "C" size_t visrep_debug_sam_table_bytes(size_t bytes) {
+    const size_t old = t_sam_table_bytes;
+    t_sam_table_bytes = bytes == 0 || bytes > SAM_TABLE_BYTES ? SAM_TABLE_BYTES : bytes;
+    return old;
+}
+
+extern "C" size_t visrep_sam_workspace_bytes(const visrep_sam_config* cfg, int B) {
+    if (!cfg || B <= 0 || sam_check(cfg)) return 0;
+    return sam_layout(cfg, B).total;
+}
+
+extern "C" int visrep_sam_forward(const visrep_sam_config* c, const visrep_sam_weights* w, const void* pixels, int pixel_dtype, void* hidden, int B,
+                                  int n_state, void* workspace, void* stream) {
+    if (!c || !w || !pixels || !hidden || !workspace || !w->layers) return visrep_set_error(VISREP_ERR_ARG, "sam_forward: null pointer");
+    if (B <= 0) return 0;
+    VR_TRY(sam_check(c));
+    if (n_state < 0 || n_state > c->layers + 1) return visrep_set_error(VISREP_ERR_ARG, "sam_forward: n_state must be 0 .. layers + 1");
+    hipStream_t s = (hipStream_t)stream;
+    const SamWs L = sam_layout(c, B);
+    char* base = (char*)workspace;
+    bf16_t* x = (bf16_t*)(base + L.x);
+    bf16_t* h = (bf16_t*)(base + L.h);
+    bf16_t* ow = (bf16_t*)(base + L.ow);
+    bf16_t* qk = (bf16_t*)(base + L.qk);
+    bf16_t* vt = (bf16_t*)(base + L.vt);
+    bf16_t* qkw = (bf16_t*)(base + L.qkw);
+    bf16_t* vtw = (bf16_t*)(base + L.vtw);
+    bf16_t* mlp = (bf16_t*)(base + L.mlp);
+    float2* rt = (float2*)(base + L.rt);
+    float2* part = (float2*)(base + L.part);
+    float* tab_h = (float*)(base + L.tab);
+    float* tab_w = (float*)(base + L.tab + SAM_TABLE_BYTES);
+    const int d = c->d, g = c->image_size / c->patch, P = g * g, M = B * P, H = c->heads, wd = c->window;
+    const float scale = 0.125f;
+
+    VR_TRY(visrep_im2col(pixels, pixel_dtype, mlp, B, c->image_size, c->image_size, c->patch, c->kpad, stream));
+    GemmArgs e{};
+    e.A = mlp; e.lda = c->kpad; e.W = (const bf16_t*)w->patch_w; e.ldw = c->kpad; e.C = x; e.ldc = d;
+    e.bias = w->patch_b; e.pos = w->pos; e.M = M; e.N = d; e.K = c->kpad; e.epi = EPI_PATCH; e.patches = P; e.tokens = P; e.cls_off = 0;
+    VR_TRY(visrep_gemm_dispatch(e, s));
+    // V^T columns that belong to no key are read with zero softmax weight: keep them finite
+    if (hipMemsetAsync(vt, 0, (size_t)d * L.ldvt * 2, s) != hipSuccess || hipMemsetAsync(vtw, 0, (size_t)d * L.ldvw * 2, s) != hipSuccess ||
+        hipMemsetAsync(rt, 0, (up(M, 256) + 8) * sizeof(float2), s) != hipSuccess)
+        return visrep_set_error(VISREP_ERR_LAUNCH, "sam_forward: memset failed");
+
+    const int n_layers = n_state > c->layers ? c->layers : n_state;
+    bool rt_ready = false;
+    for (int l = 0; l < n_layers; ++l) {
+        const visrep_sam_layer& W = w->layers[l];
+        if (!W.wqkv || !W.bqkv || !W.sqkv || !W.bqkv_raw || !W.rel_h || !W.rel_w || !W.wo || !W.w1 || !W.s1 || !W.w2)
+            return visrep_set_error(VISREP_ERR_ARG, "sam_forward: a layer's weights are missing");
+        const bool global = (c->global_mask >> l) & 1ull;
+        if (!rt_ready) VR_TRY(visrep_layernorm_stats(x, d, rt, M, d, c->eps, stream));
+        GemmArgs a{};
+        a.A = x; a.ln_rt = rt; a.ln_s = W.sqkv; a.lda = d; a.K = d; a.M = M;
+        a.W = (const bf16_t*)W.wqkv; a.ldw = d; a.N = 2 * d; a.C = qk; a.ldc = 2 * d; a.bias = W.bqkv; a.epi = EPI_BIAS;
+        VR_TRY(visrep_gemm_dispatch(a, s));
+        a.W = (const bf16_t*)W.wqkv + (size_t)2 * d * d; a.N = d; a.C = vt; a.ldc = L.ldvt; a.bias = W.bqkv + 2 * d; a.epi = EPI_VT; a.ln_s = W.sqkv + 2 * d;
+        VR_TRY(visrep_gemm_dispatch(a, s));
+        // attention over grids of side S: the whole map, or the windows of the gathered projections; in image chunks that fit the table buffer
+        const int S = global ? g : wd, T = S * S, gpi = global ? 1 : L.nw * L.nw;     // grids per image
+        const bf16_t* aq = qk; const bf16_t* av = vt; int aldv = L.ldvt; bf16_t* ao = h;
+        if (!global) {
+            VR_TRY(visrep_sam_window_partition(qk, 2 * d, vt, L.ldvt, W.bqkv_raw, qkw, 2 * d, vtw, L.ldvw, B, g, wd, d, stream));
+            aq = qkw; av = vtw; aldv = L.ldvw; ao = ow;
+        }
+        // chunk rule: as many images as fit one table buffer, at least one.  A chunk is a range of grids of the same buffers (the key tiles stay
+        // the buffers' global 64-key blocks), so the result does not depend on the chunk size.
+        const size_t per_image = (size_t)gpi * H * T * S * sizeof(float), fit = t_sam_table_bytes / per_image;
+        if (per_image > SAM_TABLE_BYTES) return visrep_set_error(VISREP_ERR_SHAPE, "sam_forward: one image's position tables exceed the table buffer");
+        const int chunk = (int)std::min<size_t>((size_t)B, std::max<size_t>(fit, 1));
+        for (int b0 = 0; b0 < B; b0 += chunk) {
+            const int nb = std::min(chunk, B - b0) * gpi;
+            const size_t r0 = (size_t)b0 * gpi * T;                 // first token row of the chunk
+            VR_TRY(visrep_relpos_tables(aq + r0 * 2 * d, 2 * d, W.rel_h, W.rel_w, tab_h, tab_w, nb, S, H, 64, stream));
+            VR_TRY(visrep_mhsa_relpos_range(aq, 2 * d, av, aldv, tab_h, tab_w, ao, d, B * gpi, b0 * gpi, nb, S, H, 64, scale, s));
+        }
+        if (!global) VR_TRY(visrep_sam_window_unpartition(ow, d, h, d, B, g, wd, d, stream));
+        a.A = h; a.lda = d; a.K = d; a.ldw = d; a.ln_rt = nullptr; a.ln_s = nullptr; a.M = M;
+        a.W = (const bf16_t*)W.wo; a.N = d; a.C = x; a.ldc = d; a.bias = W.bo; a.epi = EPI_RESID; a.resid = x; a.ls = nullptr;
+        a.stat_rt = rt; a.stat_partial = part; a.stat_eps = c->eps;
+        VR_TRY(visrep_gemm_dispatch(a, s));
+        GemmArgs f{};
+        f.A = x; f.ln_rt = rt; f.ln_s = W.s1; f.lda = d; f.K = d; f.M = M; f.W = (const bf16_t*)W.w1; f.ldw = d; f.N = c->mlp; f.C = mlp; f.ldc = c->mlp;
+        f.bias = W.b1; f.epi = EPI_ACT; f.act = VISREP_ACT_GELU_ERF;
+        VR_TRY(visrep_gemm_dispatch(f, s));
+        f.ln_rt = nullptr; f.ln_s = nullptr; f.A = mlp; f.lda = c->mlp; f.K = c->mlp; f.W = (const bf16_t*)W.w2; f.ldw = c->mlp; f.N = d; f.C = x; f.ldc = d;
+        f.bias = W.b2; f.epi = EPI_RESID; f.act = 0; f.resid = x; f.ls = nullptr;
+        const bool next = l + 1 < n_layers;
+        if (next) { f.stat_rt = rt; f.stat_partial = part; f.stat_eps = c->eps; }
+        rt_ready = next;
+        VR_TRY(visrep_gemm_dispatch(f, s));
+    }
+    if (n_state <= c->layers) {
+        if (hipMemcpyAsync(hidden, x, (size_t)M * d * 2, hipMemcpyDeviceToDevice, s) != hipSuccess) return visrep_set_error(VISREP_ERR_LAUNCH, "sam_forward: copy of the hidden state failed");
+        return 0;
+    }
+    // ---- neck: conv1x1 (no bias) -> LayerNorm over channels -> conv3x3 pad 1 (no bias) -> LayerNorm over channels
+    if (!w->neck_w1 || !w->neck_ln1_g || !w->neck_ln1_b || !w->neck_w2 || !w->neck_ln2_g || !w->neck_ln2_b)
+        return visrep_set_error(VISREP_ERR_ARG, "sam_forward: the neck's weights are missing");
+    const int oc = c->out_ch;
+    bf16_t* n1 = (bf16_t*)(base + L.neck);
+    bf16_t* n2 = n1 + up(M, 256) * (size_t)oc;
+    visrep_count_route(VISREP_ROUTE_SAM_NECK);
+    VR_TRY(visrep_gemm_bf16(x, d, w->neck_w1, d, nullptr, n1, oc, M, oc, d, VISREP_EPI_BIAS, 0, nullptr, nullptr, stream));
+    VR_TRY(visrep_layernorm(n1, oc, w->neck_ln1_g, w->neck_ln1_b, n1, oc, M, oc, c->neck_eps, stream));
+    VR_TRY(visrep_conv3x3_bf16(n1, B, g, g, oc, w->neck_w2, 9 * oc, nullptr, n2, oc, oc, 1, 0, 0, VISREP_EPI_BIAS, nullptr, stream));
+    VR_TRY(visrep_layernorm(n2, oc, w->neck_ln2_g, w->neck_ln2_b, hidden, oc, M, oc, c->neck_eps, stream));
+    return 0;
+}

@@ -116,6 +116,9 @@ extern thread_local int t_visrep_gemm_variant;   // 1 = 128x128 kernel, 2 / 5 = 
 int visrep_attention_ab_launch(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* out, int ldo,
                                int B, int Tq, int Tk, int H, int kv_shared, int causal, float scale, hipStream_t st);
 extern thread_local int t_visrep_attn_variant;
+// attention_relpos.hip: visrep_mhsa_relpos_fwd restricted to grids g0 .. g0 + nb - 1 of buffers holding NB grids (rel_h / rel_w: the nb grids' tables)
+int visrep_mhsa_relpos_range(const void* qk, int ldqk, const void* vt, int ldvt, const float* rel_h, const float* rel_w, void* out, int ldo, int NB,
+                             int g0, int nb, int S, int H, int head_dim, float scale, hipStream_t stream);
 extern thread_local int t_visrep_fuse_gate;     // A/B knob (visrep_set_fuse_gate): 1 = SwiGLU towers run fc1 with the gated epilogue, 0 = EPI_BIAS + visrep_swiglu
 int visrep_set_error(int code, const char* msg);
 // Which kernel family a call was routed to - per-THREAD launch counters read by visrep_debug_routes() (tests assert that a shape takes the

@@ -853,3 +853,115 @@ def ln_space_to_depth2_cpu(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, C:
     _lib.check(lib.visrep_ln_space_to_depth2_cpu(_lib.ptr(x), ldx, _lib.ptr(g), _lib.ptr(b), _lib.ptr(out), 4 * C, B, H, W, C, float(eps), threads),
                "visrep_ln_space_to_depth2_cpu")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ SAM ViT
+class SamEngine:
+    """One SAM ViT tower on one GPU (visrep_sam_forward): forward(pixels, n_state) returns state n_state of HF SamVisionModel as bf16 token
+    rows - 0 = patch embedding + positions, 1 .. L = the block outputs [B, g g, d], L + 1 = the neck output [B, g g, out_channels] - and stops
+    after it.  bf16 on the GPU only: there is no fp32 and no host SAM engine, and asking for one is an error, never a fallback."""
+
+    def __init__(self, spec, weights: dict, device: Optional[torch.device] = None):
+        from . import sam_weights as SW
+        if device is not None and torch.device(device).type == "cpu":
+            raise ValueError("SAM towers have no host engine (device='cpu'): only the bf16 HIP engine exists")
+        self.lib = _lib.require_gpu()
+        self.spec = spec
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.n_layers = spec.layers + 1                    # the tower protocol's name for "last hidden-state index"
+        self.kpad = _round_up(3 * spec.patch * spec.patch, 64)
+        ensure_scratch(self.device)
+        self._keep = []
+
+        def dev(t):
+            x = t.detach().to(device=self.device).contiguous()
+            self._keep.append(x)
+            return x.data_ptr()
+
+        if len(weights["layers"]) != spec.layers:
+            raise ValueError(f"weights have {len(weights['layers'])} layers, spec wants {spec.layers}")
+        D = SW.device_layout(spec, weights, self.kpad)
+        self._layers = (_lib.SamLayer * spec.layers)()
+        for i, L in enumerate(D["layers"]):
+            for k, _ in _lib.SamLayer._fields_:
+                setattr(self._layers[i], k, dev(L[k]))
+        self._w = _lib.SamWeights()
+        for k, _ in _lib.SamWeights._fields_[:-1]:
+            setattr(self._w, k, dev(D[k]))
+        self._w.layers = C.cast(self._layers, C.POINTER(_lib.SamLayer))
+        mask = 0
+        for i in spec.global_attn_indexes:
+            mask |= 1 << i
+        self._cfg = _lib.SamConfig(spec.image_size, spec.patch, spec.d, spec.layers, spec.heads, spec.mlp, spec.window, spec.out_channels, self.kpad,
+                                   mask, float(spec.eps), 1e-6)
+        self._ws: Dict[int, torch.Tensor] = {}
+
+    def workspace(self, B: int) -> torch.Tensor:
+        ws = self._ws.get(B)
+        if ws is None:
+            nbytes = self.lib.visrep_sam_workspace_bytes(C.byref(self._cfg), B)
+            if nbytes == 0:
+                raise RuntimeError(f"visrep_sam_workspace_bytes refused the tower: {_lib.last_error()}")
+            self._ws.clear()
+            ws = self._ws[B] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        return ws
+
+    @torch.no_grad()
+    def forward(self, pixels: torch.Tensor, n_state: Optional[int] = None, out: Optional[torch.Tensor] = None, n_layers: Optional[int] = None) -> torch.Tensor:
+        s = self.spec
+        if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != s.image_size or pixels.shape[3] != s.image_size:
+            raise ValueError(f"Input image size {tuple(pixels.shape)} doesn't match tower ({s.image_size}*{s.image_size}).")
+        if n_state is None:
+            n_state = s.layers + 1 if n_layers is None else n_layers
+        if not 0 <= n_state <= s.layers + 1:
+            raise ValueError(f"n_state out of range (0 = embeddings, 1 .. {s.layers} = blocks, {s.layers + 1} = the neck)")
+        px = pixels.to(self.device)
+        if px.dtype not in (torch.float32, torch.bfloat16):
+            px = px.float()
+        px = px.contiguous()
+        B = px.shape[0]
+        if out is None:
+            out = torch.empty(B, s.grid ** 2, s.width(n_state), dtype=torch.bfloat16, device=self.device)
+        ws = self.workspace(B)
+        with torch.cuda.device(self.device):
+            rc = self.lib.visrep_sam_forward(C.byref(self._cfg), C.byref(self._w), _lib.ptr(px), _lib.F32 if px.dtype == torch.float32 else _lib.BF16,
+                                             _lib.ptr(out), B, n_state, _lib.ptr(ws), _lib.stream_ptr())
+        _lib.check(rc, "visrep_sam_forward")
+        return out
+
+
+def make_sam_engine(spec, weights: dict, device=None, precision: str = "bf16") -> SamEngine:
+    """make_engine for SAM towers: bf16 on the GPU, and a ValueError that says so for anything else."""
+    if precision not in ("bf16", "bfloat16"):
+        raise ValueError(f"SAM towers run in bf16 only: there is no {precision} SAM engine (a full fp32 engine is out of scope)")
+    return SamEngine(spec, weights, device)
+
+
+def relpos_tables(qk: torch.Tensor, Rh: torch.Tensor, Rw: torch.Tensor, NB: int, S: int, H: int, out=None):
+    """qk [NB S S, ldqk] bf16 (Q in the first H 64 columns), Rh / Rw [2 S - 1, 64] fp32 -> (rel_h, rel_w) fp32 [NB, H, S S, S] - visrep_relpos_tables
+    on the GPU, its host twin for host tensors.  out: a (rel_h, rel_w) pair to write into instead of allocating."""
+    T = S * S
+    if out is not None:
+        rel_h, rel_w = out
+    else:
+        rel_h = torch.empty(NB, H, T, S, dtype=torch.float32, device=qk.device)
+        rel_w = torch.empty_like(rel_h)
+    if qk.device.type == "cpu":
+        _lib.check(_lib.load().visrep_relpos_tables_cpu(_lib.ptr(qk), qk.stride(0), _lib.ptr(Rh), _lib.ptr(Rw), _lib.ptr(rel_h), _lib.ptr(rel_w), NB, S, H,
+                                                        64, 0), "visrep_relpos_tables_cpu")
+        return rel_h, rel_w
+    lib = _lib.require_gpu()
+    with torch.cuda.device(qk.device):
+        _lib.check(lib.visrep_relpos_tables(_lib.ptr(qk), qk.stride(0), _lib.ptr(Rh), _lib.ptr(Rw), _lib.ptr(rel_h), _lib.ptr(rel_w), NB, S, H, 64,
+                                            _lib.stream_ptr()), "visrep_relpos_tables")
+    return rel_h, rel_w
+
+
+def mhsa_relpos(qk: torch.Tensor, vt: torch.Tensor, rel_h: torch.Tensor, rel_w: torch.Tensor, NB: int, S: int, H: int, scale: float = 0.125) -> torch.Tensor:
+    """visrep_mhsa_relpos_fwd: qk [NB S S, ldqk] bf16, vt [H 64, ldvt] bf16 (VISREP_EPI_VT layout), tables fp32 [NB, H, S S, S] -> [NB S S, H 64] bf16."""
+    lib = _lib.require_gpu()
+    out = torch.empty(NB * S * S, H * 64, dtype=torch.bfloat16, device=qk.device)
+    with torch.cuda.device(qk.device):
+        _lib.check(lib.visrep_mhsa_relpos_fwd(_lib.ptr(qk), qk.stride(0), _lib.ptr(vt), vt.stride(0), _lib.ptr(rel_h), _lib.ptr(rel_w), _lib.ptr(out),
+                                              out.stride(0), NB, S, H, 64, float(scale), _lib.stream_ptr()), "visrep_mhsa_relpos_fwd")
+    return out

@@ -13,6 +13,7 @@ from .convnext_encoder import ConvNextVisionTower
 from .diffLVLM.diffusion_encoder import DiffVisionTower
 from .dinov2_encoder import DinoV2VisionTower
 from .internvit_encoder import InternViTVisionTower
+from .sam_encoder import SamVisionTower
 from .siglip_encoder import SigLipVisionTower
 
 _CLIP_PREFIXES = ("openai", "laion")
@@ -50,6 +51,11 @@ def build_internvit_vision_tower(vision_tower_cfg, **kwargs):
 def build_convnext_vision_tower(vision_tower_cfg, **kwargs):
     """ConvNeXt (HF ConvNextModel, OpenCLIP's convnext_* trunks).  Not a reference registry entry: add the id to llava_arch.build_function_mapping."""
     return _make(ConvNextVisionTower, vision_tower_cfg, kwargs)
+
+
+def build_sam_vision_tower(vision_tower_cfg, **kwargs):
+    """SAM ViT (HF SamVisionModel: sam-vit-base / sam-vit-large).  Not a reference registry entry: add the id to llava_arch.build_function_mapping."""
+    return _make(SamVisionTower, vision_tower_cfg, kwargs)
 
 
 def build_diffusion_vision_tower(vision_tower_cfg, **kwargs):

@@ -17,6 +17,9 @@
   6. the ConvNeXt kernels (dwconv.hip: both dwconv7x7_stats_tile shapes, ln_stats_finalize_rows_odd, ln_space_to_depth2_rows) exist and use no
      scratch: 64 accumulators + 56 weights per lane (dwconv), a row of up to 4096 columns in 64 registers (space-to-depth).
 
+  7. the SAM kernels (attention_relpos.hip: attn_fwd_relpos, relpos_tables_rows, the two sam_window_partition kernels and
+     sam_window_unpartition_rows) exist and use no scratch: the position tables live in LDS, never in an indexed register array.
+
 usage: python tools/isa_check.py [--sizes] [file.hip ...]      (default: the product library's persistent kernels)
 --sizes also prints every kernel's code length (to compare the existing instantiations with a parent build)."""
 import os
@@ -28,13 +31,14 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "law_of_vision_representation_in_mllms_amd", "csrc")
 SIZES = "--sizes" in sys.argv[1:]
-FILES = [a for a in sys.argv[1:] if a != "--sizes"] or ["gemm_bf16_v5.hip", "gemm_bf16_v2.hip", "ascore.hip", "attention.hip", "rowops.hip", "gemm_bf16.hip", "dwconv.hip"]
+FILES = [a for a in sys.argv[1:] if a != "--sizes"] or ["gemm_bf16_v5.hip", "gemm_bf16_v2.hip", "ascore.hip", "attention.hip", "rowops.hip", "gemm_bf16.hip", "dwconv.hip", "attention_relpos.hip"]
 # kernels (by name fragment) that must not touch scratch; Li7E = template argument EPI_GATED of gemm_bf16_256q / gemm_bf16_256
 RMS_KERNELS = ("8rms_rows", "14rms_stats_rows", "23rms_stats_finalize_rows", "15qk_rmsnorm_rows", "12rms_f32_rows")
 CONVNEXT_KERNELS = ("20dwconv7x7_stats_tileILi8ELi8EE", "20dwconv7x7_stats_tileILi16ELi16EE", "26ln_stats_finalize_rows_odd", "23ln_space_to_depth2_rows")
-NO_SCRATCH = ("attn_fwd", "gemm_bf16_256qILi7E", "gemm_bf16_256ILi7E", "17splitk_reduce_rms") + RMS_KERNELS + CONVNEXT_KERNELS
+SAM_KERNELS = ("15attn_fwd_relpos", "18relpos_tables_rows", "23sam_window_partition_qk", "23sam_window_partition_vt", "27sam_window_unpartition_rows")
+NO_SCRATCH = ("attn_fwd", "gemm_bf16_256qILi7E", "gemm_bf16_256ILi7E", "17splitk_reduce_rms") + RMS_KERNELS + CONVNEXT_KERNELS + SAM_KERNELS
 REQUIRED = {"gemm_bf16_v5.hip": ("gemm_bf16_256qILi7ELb1E", "gemm_bf16_256qILi7ELb0E"), "gemm_bf16_v2.hip": ("gemm_bf16_256ILi7E",),
-            "rowops.hip": RMS_KERNELS, "gemm_bf16.hip": ("17splitk_reduce_rms",), "dwconv.hip": CONVNEXT_KERNELS}
+            "rowops.hip": RMS_KERNELS, "gemm_bf16.hip": ("17splitk_reduce_rms",), "dwconv.hip": CONVNEXT_KERNELS, "attention_relpos.hip": SAM_KERNELS}
 bad = 0
 for f in FILES:
     with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
