@@ -168,7 +168,9 @@ int visrep_set_gemm_walk(int code);
  * (llava/model/multimodal_projector/builder.py:40-47).
  * A [M,K] bf16 (lda), W [N,K] bf16 (ldw, nn.Linear layout), bias [N] fp32 or NULL, C [M,N] bf16 (fp32 for EPI_F32).
  * N % 128 == 0, K % 64 == 0.  resid (bf16, same shape/ld as C, may alias C) and ls (fp32 [N] or NULL) are used by
- * EPI_RESID only. */
+ * EPI_RESID only.  C and resid must be 8-byte aligned (C 16-byte for EPI_F32) and ldc % 4 == 0 - a column window at a multiple of 4 elements
+ * of an aligned buffer; anything less is refused before a launch, here and by the _ln, _rows and _resid_stats entries below.  16-byte aligned
+ * C (and resid) with ldc % 8 == 0 selects the 16-byte store path. */
 int visrep_gemm_bf16(const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc, int M, int N, int K,
                      int epilogue, int act, const void* resid, const float* ls, void* stream);
 
@@ -194,7 +196,9 @@ int visrep_gemm_bf16_ln(const void* A, int lda, const void* W, int ldw, const fl
 /* A GEMM over a periodic subset of A's rows: logical row r reads physical row (r / row_period) * row_stride + r % row_period + row_first
  * (e.g. the patch tokens of every image: period T - 1, stride T, first 1 - the reference's feature_select `[:, 1:]`,
  * clip_encoder.py:37-44 - or the CLS rows: period 1, stride T, first 0) without gathering them first.  ln_rt / ln_s (both or neither):
- * folded LayerNorm, statistics indexed by PHYSICAL row.  Epilogues BIAS, ACT, VT (row_period % 4 == 0), F32. */
+ * folded LayerNorm, statistics indexed by PHYSICAL row.  Epilogues BIAS, ACT, VT (row_period % 4 == 0), F32.  A folded VT reads the statistics
+ * of four consecutive physical rows per 4-token group: when M % 4 != 0 the last group reads up to 3 entries past the last mapped row, so ln_rt
+ * needs the same padding as for visrep_gemm_bf16_ln (round_up(physical rows, 128) + 8 entries; their values are never stored). */
 int visrep_gemm_bf16_rows(const void* A, int lda, int row_period, int row_stride, int row_first, const void* W, int ldw, const float* bias,
                           const void* ln_rt, const float* ln_s, void* C, int ldc, int M, int N, int K, int epilogue, int act, void* stream);
 int visrep_gemm_bf16_resid_stats(const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc, int M, int N, int K,

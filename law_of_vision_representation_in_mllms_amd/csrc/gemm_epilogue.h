@@ -556,8 +556,9 @@ VR_DEV void gemm_epilogue_vt_impl(const GemmArgs& p, const ACC (&acc)[NI][NJ], i
                 for (int q = 0; q < QN; ++q) {
                     const int m = mb + (i0 + i) * RBLK + q * 8 + hg * 4;
                     // four consecutive tokens: consecutive physical rows too (a row map's period is a multiple of 4).  Rows past M read the zero
-                    // padding of the statistics buffer; with a row map they are clamped to the last four rows instead (never stored either way)
-                    const float4* src = reinterpret_cast<const float4*>(p.ln_rt + visrep_a_row(p, (p.a_period > 0 && m + 4 > p.M) ? p.M - 4 : m));
+                    // padding of the statistics buffer; with a row map, groups that lie wholly past M (never stored) are clamped to the last four
+                    // rows instead.  A group that straddles M (M % 4 != 0) keeps its own rows: its tokens below M are stored.
+                    const float4* src = reinterpret_cast<const float4*>(p.ln_rt + visrep_a_row(p, (p.a_period > 0 && m >= p.M) ? (p.M > 4 ? p.M - 4 : 0) : m));
                     ra[i * QN + q] = src[0];                // (rstd0, t0, rstd1, t1)
                     rb[i * QN + q] = src[1];                // (rstd2, t2, rstd3, t3)
                 }

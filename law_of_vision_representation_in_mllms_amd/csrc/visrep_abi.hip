@@ -150,11 +150,24 @@ extern "C" int visrep_set_stream_scratch(void* stream, void* ptr, size_t bytes) 
     return visrep_scratch_register(false, (hipStream_t)stream, ptr, bytes);   // keyed by (current device, stream)
 }
 
+// Output / residual alignment the GEMM epilogues are written for (8-byte stores and residual loads at the least; fp32 outputs are stored
+// 16 bytes at a time).  Every in-tree caller passes whole rows of an allocation or a column window at a multiple of 4 elements; anything less
+// is refused before a launch, as visrep_gemm_bf16_gated always did.
+static int gemm_refuse_misaligned(const char* who, const void* C, const void* resid, bool f32_out) {   // 0 = aligned, else the error code
+    const char* why = ((uintptr_t)C & (f32_out ? 15 : 7)) ? (f32_out ? "C must be 16-byte aligned for EPI_F32" : "C must be 8-byte aligned")
+                      : ((uintptr_t)resid & 7) ? "resid must be 8-byte aligned" : nullptr;
+    if (!why) return 0;
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s: %s", who, why);
+    return visrep_set_error(VISREP_ERR_ARG, msg);
+}
+
 extern "C" int visrep_gemm_bf16(const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc, int M, int N,
                                 int K, int epilogue, int act, const void* resid, const float* ls, void* stream) {
     if (!A || !W || !C) return visrep_set_error(VISREP_ERR_ARG, "gemm: null pointer");
     if (epilogue == VISREP_EPI_PATCH) return visrep_set_error(VISREP_ERR_ARG, "gemm: EPI_PATCH is internal to visrep_vit_forward");
     if (epilogue == VISREP_EPI_RESID && !resid) return visrep_set_error(VISREP_ERR_ARG, "gemm: EPI_RESID needs resid");
+    if (const int rc = gemm_refuse_misaligned("gemm", C, epilogue == VISREP_EPI_RESID ? resid : nullptr, epilogue == VISREP_EPI_F32)) return rc;
     GemmArgs a{};
     a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = (bf16_t*)C; a.bias = bias;
     a.resid = (const bf16_t*)resid; a.ls = ls; a.pos = nullptr;
@@ -167,6 +180,7 @@ extern "C" int visrep_gemm_bf16_ln(const void* A, int lda, const void* W, int ld
     if (!A || !W || !C || !ln_rt || !ln_s) return visrep_set_error(VISREP_ERR_ARG, "gemm_ln: null pointer");
     if (epilogue != VISREP_EPI_BIAS && epilogue != VISREP_EPI_ACT && epilogue != VISREP_EPI_VT)
         return visrep_set_error(VISREP_ERR_ARG, "gemm_ln: epilogue must be BIAS, ACT or VT");
+    if (const int rc = gemm_refuse_misaligned("gemm_ln", C, nullptr, false)) return rc;
     GemmArgs a{};
     a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = (bf16_t*)C; a.bias = bias; a.ln_rt = (const float2*)ln_rt; a.ln_s = ln_s;
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.epi = epilogue; a.act = act;
@@ -215,6 +229,7 @@ extern "C" int visrep_gemm_bf16_rows(const void* A, int lda, int row_period, int
     if (!A || !W || !C || ((ln_rt == nullptr) != (ln_s == nullptr))) return visrep_set_error(VISREP_ERR_ARG, "gemm_rows: null pointer");
     if (row_period <= 0 || row_stride < row_period || row_first < 0) return visrep_set_error(VISREP_ERR_ARG, "gemm_rows: bad row map");
     if (epilogue == VISREP_EPI_VT && row_period % 4) return visrep_set_error(VISREP_ERR_ARG, "gemm_rows: EPI_VT needs row_period % 4 == 0");
+    if (const int rc = gemm_refuse_misaligned("gemm_rows", C, nullptr, epilogue == VISREP_EPI_F32)) return rc;
     GemmArgs a{};
     a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = (bf16_t*)C; a.bias = bias; a.ln_rt = (const float2*)ln_rt; a.ln_s = ln_s;
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.epi = epilogue; a.act = act;
@@ -226,6 +241,7 @@ extern "C" int visrep_gemm_bf16_resid_stats(const void* A, int lda, const void* 
                                             int K, const void* resid, const float* ls, void* rt, void* partial, float eps, void* stream) {
     if (!A || !W || !C || !resid || !rt || !partial) return visrep_set_error(VISREP_ERR_ARG, "gemm_resid_stats: null pointer");
     if (N > 2048) return visrep_set_error(VISREP_ERR_SHAPE, "gemm_resid_stats: N <= 2048");
+    if (const int rc = gemm_refuse_misaligned("gemm_resid_stats", C, resid, false)) return rc;
     GemmArgs a{};
     a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = (bf16_t*)C; a.bias = bias; a.resid = (const bf16_t*)resid; a.ls = ls;
     a.stat_rt = (float2*)rt; a.stat_partial = (float2*)partial; a.stat_eps = eps;
