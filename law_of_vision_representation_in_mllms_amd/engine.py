@@ -5,6 +5,7 @@ PyTorch is used for device memory and streams only; every FLOP of the forward ru
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, Optional
 
 import torch
@@ -94,7 +95,113 @@ def ensure_scratch(device, nbytes: int = 64 << 20) -> None:
         _SCRATCH[idx] = buf
 
 
-class VitEngine:
+class _TowerEngine:
+    """What every tower engine does on the host side of the library: it resolves the device, keeps the tensors whose raw pointers the tables
+    hold, checks and converts a pixel batch, range-checks the state index and caches workspaces per batch size; an engine with a workspace
+    supplies _workspace_bytes(B)."""
+
+    WS_KEEP = 5                                            # unpinned workspaces that stay resident beside the one being asked for
+    WS_ZERO = True                                         # the forward expects a zero-filled workspace
+    PIXEL_DTYPES = (torch.float32, torch.bfloat16)         # what the forward reads as it is; every other pixel dtype is cast to fp32
+
+    def __init__(self, lib, spec, device):
+        self.lib = lib
+        self.spec = spec
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self._keep = []                      # tensors referenced by raw pointers, in packing order (sweep.tower_fingerprint hashes them in it)
+        self._ws: Dict[int, torch.Tensor] = {}
+        self._pinned = set()                 # batch sizes whose workspace a captured HIP graph refers to
+
+    def _hold(self, t, dtype=None):
+        """`t` on the engine's device (as `dtype`, if given), contiguous and kept alive; None stays None."""
+        if t is None:
+            return None
+        x = t.detach().to(device=self.device, dtype=dtype).contiguous()
+        self._keep.append(x)
+        return x
+
+    def _pixels(self, pixels: torch.Tensor) -> torch.Tensor:
+        side = self.spec.image_size
+        if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != side or pixels.shape[3] != side:
+            raise ValueError(f"Input image size {tuple(pixels.shape)} doesn't match tower ({side}*{side}).")
+        px = pixels.to(self.device)
+        if px.dtype not in self.PIXEL_DTYPES:
+            px = px.float()
+        return px.contiguous()
+
+    def _state(self, n: Optional[int], message: str) -> int:
+        """The hidden-state index a forward stops at: None = the last one, anything outside 0 .. n_layers is `message`."""
+        n = self.n_layers if n is None else n
+        if not 0 <= n <= self.n_layers:
+            raise ValueError(message)
+        return n
+
+    def _allocate(self, nbytes: int) -> torch.Tensor:
+        return (torch.zeros if self.WS_ZERO else torch.empty)(nbytes, dtype=torch.uint8, device=self.device)
+
+    def workspace(self, B: int) -> torch.Tensor:
+        """The workspace of batch size B.  WS_KEEP unpinned ones stay resident beside it, oldest dropped first (before the new one is allocated:
+        with WS_KEEP = 0 two never coexist).  One that a HIP graph captured (the image-variation featurizer records a forward inside its own
+        graph) is PINNED: a replayed graph keeps using the pointer it saw, so it is never dropped."""
+        ws = self._ws.get(B)
+        if ws is None:
+            nbytes = self._workspace_bytes(B)
+            unpinned = [b for b in self._ws if b not in self._pinned]
+            for old in unpinned[: max(0, len(unpinned) - self.WS_KEEP)]:
+                self._ws.pop(old)
+            ws = self._ws[B] = self._allocate(nbytes)
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            self._pinned.add(B)
+        return ws
+
+
+def _addr(t: Optional[torch.Tensor]) -> int:
+    return 0 if t is None else t.data_ptr()
+
+
+_VIT_MATRICES = ("wqkv", "wo", "w1", "w2")
+_VIT_VECTORS = ("ln1_g", "ln1_b", "bqkv", "bo", "ls1", "ln2_g", "ln2_b", "b1", "b2", "ls2", "sqkv", "s1")
+
+
+def _vit_vector_table(spec: ViTSpec, weights: dict) -> dict:
+    """The tower-level vectors of VitWeights; cls = [d], or [1 + registers, d]: the class token, then the register tokens."""
+    return {**{k: weights.get(k) for k in ("patch_b", "pos", "pre_ln_g", "pre_ln_b")}, "cls": prefix_table(spec, weights)}
+
+
+def _fill_vit_tables(eng: _TowerEngine, patch_w: torch.Tensor, vecs: dict, layers, mat_dtype=torch.float32) -> list:
+    """Upload a ViT tower and fill what visrep_vit_forward* read: eng._w (VitWeights), eng._layers (the VitLayer array, eng.n_layers long) and
+    eng._vecs.  Tensors enter eng._keep as patch matrix, vector table, then per layer the four matrices (as `mat_dtype`), the fp32 vectors,
+    sqkv / s1 and - QK-norm towers - the two gains.  `layers`: one dict per layer, absent or None entries = null pointers; a generator keeps
+    one prepared layer on the host at a time.  Returns, per layer, name -> the tensor held."""
+    eng._patch_w = eng._hold(patch_w, mat_dtype)
+    eng._vecs = {k: eng._hold(v, torch.float32) for k, v in vecs.items()}
+    eng._layers = (_lib.VitLayer * max(eng.n_layers, 1))()
+    names = _VIT_MATRICES + _VIT_VECTORS + (("qn_g", "kn_g") if eng.spec.qk_norm else ())
+    held = []
+    for ent, L in zip(eng._layers, layers):
+        held.append({k: eng._hold(L.get(k), mat_dtype if k in _VIT_MATRICES else torch.float32) for k in names})
+        for k, v in held[-1].items():
+            setattr(ent, k, _addr(v))
+    eng._w = _lib.VitWeights(patch_w=eng._patch_w.data_ptr(), layers=C.cast(eng._layers, C.POINTER(_lib.VitLayer)))
+    for k, v in eng._vecs.items():
+        setattr(eng._w, k, _addr(v))
+    return held
+
+
+def _raw_vit_layers(spec: ViTSpec, weights: dict):
+    """The packed layers as the fp32 engines take them: untouched, absent QK gains = ones."""
+    for L in weights["layers"]:
+        if spec.qk_norm:
+            L = {**L, **{k: torch.ones(spec.d) for k in ("qn_g", "kn_g") if L.get(k) is None}}
+        yield L
+
+
+def _plain_vit_config(spec: ViTSpec, n: int, kpad: int):
+    return _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, spec.mlp, n, spec.tokens, int(spec.has_cls), int(spec.pre_ln),
+                          _lib.ACT[spec.act], kpad, float(spec.eps), registers=spec.registers, norm=_lib.NORM[spec.norm], qk_norm=int(spec.qk_norm))
+
+
+class VitEngine(_TowerEngine):
     """One ViT tower on one GPU.
 
     forward(pixels, n_layers) returns hidden_states[n_layers] as a bf16 tensor [B, tokens, d]
@@ -116,14 +223,11 @@ class VitEngine:
         first LayerNorm runs the read-only statistics pass.  Measured on ViT-L/14-336, batch 256: the two LayerNorm passes per
         layer (19.7 ms of kernel time per 4 forwards) are replaced by 15.2 ms of heavier epilogues + partial-sum reduction:
         +0.8 % kernel time, +1.4 % on the bench line (profiles/round1_fold_stats.md)."""
-        self.lib = _lib.require_gpu()
-        import os
+        super().__init__(_lib.require_gpu(), spec, device)
         self.fuse_ln = (os.environ.get("VISREP_FUSE_LN", "1") != "0") if fuse_ln is None else bool(fuse_ln)
         # SwiGLU towers (DINOv2-giant): fc1 with the gate in the GEMM epilogue (default; w1 / b1 / s1 in the 16-row interleave) or, with
         # fuse_gate=False / VISREP_FUSE_GATE=0, as a plain GEMM + the element-wise visrep_swiglu pass (A/B baseline, profiles/swiglu.md)
         self.fuse_gate = (os.environ.get("VISREP_FUSE_GATE", "1") != "0") if fuse_gate is None else bool(fuse_gate)
-        self.spec = spec
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         if spec.d % spec.heads:
             raise ValueError("d must be a multiple of heads")
         self.head_dim = spec.d // spec.heads
@@ -136,31 +240,11 @@ class VitEngine:
         da = spec.heads * self.head_pad
         ensure_scratch(self.device)
         self.kpad = _round_up(3 * spec.patch * spec.patch, 64)
-        self._keep = []          # device tensors referenced by raw pointers
-        dev = self.device
-
-        def mat(t):              # bf16 [out, in]
-            x = t.detach().to(device=dev, dtype=torch.bfloat16).contiguous()
-            self._keep.append(x)
-            return x
-
-        def vec(t):              # fp32 vector
-            if t is None:
-                return None
-            x = t.detach().to(device=dev, dtype=torch.float32).contiguous()
-            self._keep.append(x)
-            return x
-
         pw = torch.zeros(spec.d, self.kpad, dtype=torch.float32)
         pw[:, : 3 * spec.patch * spec.patch] = weights["patch_w"].float()
         if weights["pos"].shape[0] != spec.tokens:
             raise ValueError(f"position embedding has {weights['pos'].shape[0]} rows, spec wants {spec.tokens}")
-        self._patch_w = mat(pw)
-        self._vecs = {k: vec(weights.get(k)) for k in ("patch_b", "pos", "pre_ln_g", "pre_ln_b")}
-        self._vecs["cls"] = vec(prefix_table(spec, weights))      # [d], or [1 + registers, d]: the class token, then the register tokens
-        n = len(weights["layers"])
-        self.n_layers = n
-        self._layers = (_lib.VitLayer * max(n, 1))()
+        self.n_layers = n = len(weights["layers"])
         # softmax scale in the exponent's base, folded into the Q rows of the Q|K|V projection (attn_fwd PS): q' = c * q with
         # c = head_dim^-0.5 * log2(e), so that 2^(q'.k) = e^(q.k / sqrt(head_dim)).  VISREP_Q_PRESCALE=0 keeps the scale in the kernel.
         # VISREP_Q_PRESCALE=2 (default) additionally lets towers with a CLS token and 64 n patches run the image-aligned attention kernel.
@@ -182,75 +266,43 @@ class VitEngine:
             shift = Wb @ b.detach().float()                                  # beta pushed through the linear map
             return Wf, Wf.float().sum(1), (shift if bias is None else shift + bias.detach().float()) * rs
 
-        for i, L in enumerate(weights["layers"]):
-            ent = self._layers[i]
+        def device_layer(L):
             L = pad_tower_weights(spec, L, self.head_pad, self.mlp_pad)       # before the fold: it sees the padded matrices (zero rows: s = 0, b' = 0)
-            extra = {"sqkv": None, "s1": None}
+            L["sqkv"] = L["s1"] = None
             if self.fuse_ln:                                                   # RMSNorm blocks: gamma only, no beta term (sqkv / s1 stay finite and meet a zero factor)
                 nb = torch.zeros(spec.d) if spec.norm == "rmsnorm" else None
-                L["wqkv"], extra["sqkv"], L["bqkv"] = fold(L["wqkv"], L.get("bqkv"), L["ln1_g"], L["ln1_b"] if nb is None else nb, qc)
-                L["w1"], extra["s1"], L["b1"] = fold(L["w1"], L.get("b1"), L["ln2_g"], L["ln2_b"] if nb is None else nb)
+                L["wqkv"], L["sqkv"], L["bqkv"] = fold(L["wqkv"], L.get("bqkv"), L["ln1_g"], L["ln1_b"] if nb is None else nb, qc)
+                L["w1"], L["s1"], L["b1"] = fold(L["w1"], L.get("b1"), L["ln2_g"], L["ln2_b"] if nb is None else nb)
             elif self.q_prescaled and not spec.qk_norm:                        # unfused path: scale the (bf16-rounded) rows, round once more
                 L["wqkv"] = L["wqkv"].detach().float().to(torch.bfloat16).float() * qc[:, None]
                 if L.get("bqkv") is not None:
                     L["bqkv"] = L["bqkv"].detach().float() * qc
             if spec.act == "swiglu" and self.fuse_gate:                        # after the fold (per row): w1, b1 and s1 move together
                 idx = swiglu_interleave_index(self.mlp_pad)
-                L["w1"] = L["w1"][idx]
-                if L.get("b1") is not None:
-                    L["b1"] = L["b1"][idx]
-                if extra["s1"] is not None:
-                    extra["s1"] = extra["s1"][idx]
-            for k in ("wqkv", "wo", "w1", "w2"):
-                setattr(ent, k, mat(L[k]).data_ptr())
-            for k in ("ln1_g", "ln1_b", "bqkv", "bo", "ls1", "ln2_g", "ln2_b", "b1", "b2", "ls2"):
-                v = vec(L.get(k))
-                setattr(ent, k, 0 if v is None else v.data_ptr())
-            for k, t in extra.items():
-                v = vec(t)
-                setattr(ent, k, 0 if v is None else v.data_ptr())
+                for k in ("w1", "b1", "s1"):
+                    if L.get(k) is not None:
+                        L[k] = L[k][idx]
             if spec.qk_norm:                                                   # fp32 gains, padded per head; the pre-scaled-Q constant rides on qn_g
-                ent.qn_g = vec(pad_qk_gain(spec, L.get("qn_g"), self.head_pad) * (q_const if self.q_prescaled else 1.0)).data_ptr()
-                ent.kn_g = vec(pad_qk_gain(spec, L.get("kn_g"), self.head_pad)).data_ptr()
-        self._w = _lib.VitWeights()
-        self._w.patch_w = self._patch_w.data_ptr()
-        for k, v in self._vecs.items():
-            setattr(self._w, k, 0 if v is None else v.data_ptr())
-        self._w.layers = C.cast(self._layers, C.POINTER(_lib.VitLayer))
+                L["qn_g"] = pad_qk_gain(spec, L.get("qn_g"), self.head_pad) * (q_const if self.q_prescaled else 1.0)
+                L["kn_g"] = pad_qk_gain(spec, L.get("kn_g"), self.head_pad)
+            return L
+
+        _fill_vit_tables(self, pw, _vit_vector_table(spec, weights), map(device_layer, weights["layers"]), torch.bfloat16)
         self._cfg = _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, self.mlp_pad, n, spec.tokens,
                                    int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), self._q_mode,
                                    self.head_dim, self.head_pad, spec.registers, _lib.NORM[spec.norm], int(spec.qk_norm))
-        self._ws: Dict[int, torch.Tensor] = {}
-        self._pinned = set()                 # batch sizes whose workspace a captured HIP graph refers to
 
-    def workspace(self, B: int) -> torch.Tensor:
-        ws = self._ws.get(B)
-        if ws is None:
-            old_knob = self.lib.visrep_set_fuse_gate(int(self.fuse_gate))          # the unfused SwiGLU route keeps a wider MLP buffer
-            nbytes = self.lib.visrep_vit_workspace_bytes(C.byref(self._cfg), B)
-            self.lib.visrep_set_fuse_gate(old_knob)
-            # a few batch sizes stay resident; a workspace that a HIP graph captured (the image-variation featurizer records this engine's
-            # forward inside its own graph) is PINNED: a replayed graph keeps using the pointer it saw, so it is never evicted
-            for old in [b for b in self._ws if b not in self._pinned][: max(0, len(self._ws) - len(self._pinned) - 5)]:
-                self._ws.pop(old)
-            ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-            self._ws[B] = ws
-        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            self._pinned.add(B)
-        return ws
+    def _workspace_bytes(self, B: int) -> int:
+        old_knob = self.lib.visrep_set_fuse_gate(int(self.fuse_gate))              # the unfused SwiGLU route keeps a wider MLP buffer
+        nbytes = self.lib.visrep_vit_workspace_bytes(C.byref(self._cfg), B)
+        self.lib.visrep_set_fuse_gate(old_knob)
+        return nbytes
 
     @torch.no_grad()
     def forward(self, pixels: torch.Tensor, n_layers: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         s = self.spec
-        if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != s.image_size or pixels.shape[3] != s.image_size:
-            raise ValueError(f"Input image size {tuple(pixels.shape)} doesn't match tower ({s.image_size}*{s.image_size}).")
-        n_layers = self.n_layers if n_layers is None else n_layers
-        if not 0 <= n_layers <= self.n_layers:
-            raise ValueError("n_layers out of range")
-        px = pixels.to(self.device)
-        if px.dtype not in (torch.float32, torch.bfloat16):
-            px = px.float()
-        px = px.contiguous()
+        px = self._pixels(pixels)
+        n_layers = self._state(n_layers, "n_layers out of range")
         B = px.shape[0]
         if out is None:
             out = torch.empty(B, s.tokens, s.d, dtype=torch.bfloat16, device=self.device)
@@ -265,7 +317,7 @@ class VitEngine:
         return out
 
 
-class VitEngineF32:
+class VitEngineF32(_TowerEngine):
     """The same tower in reference precision: fp32 weights, activations and accumulation (csrc/f32ops.hip, visrep_vit_forward_f32).
 
     The reference's C-score CLIP / OpenCLIP / DINOv2 towers run in fp32 (C_score/extract_feature.py:36-45,49-50: no dtype cast,
@@ -273,6 +325,9 @@ class VitEngineF32:
     1/6 of the bf16 engine's throughput on the split-bf16 route (1/10 on the exact-fp32 MFMA route, which takes any head width that is a
     multiple of 4).
     forward() returns fp32 [B, tokens, d]; images are processed in chunks so that the fp32 score matrices stay below `max_ws_bytes`."""
+
+    WS_ZERO = False
+    PIXEL_DTYPES = (torch.float32,)
 
     def __init__(self, spec: ViTSpec, weights: dict, device: Optional[torch.device] = None, max_ws_bytes: int = 8 << 30, gemm: str = "auto",
                  products: Optional[int] = None):
@@ -283,53 +338,18 @@ class VitEngineF32:
         4 / 3 = two planes (16 significand bits), all four pairs / without (mid, mid): ~4e-6 per product sum at half the matrix work.
         None = DEFAULT_SPLIT_PRODUCTS = 6, the fp32-equivalent set (3 holds A <= 1e-4 and exact PCK hits on the full-size SYNTHETIC towers,
         profiles/round4_precision.md, and is the sweep's explicit opt-in); VISREP_F32_PRODUCTS in the environment overrides."""
-        self.lib = _lib.require_gpu()
-        self.spec = spec
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        super().__init__(_lib.require_gpu(), spec, device)
         if spec.d % spec.heads or (spec.d // spec.heads) % 4 or spec.mlp % 4:
             raise ValueError("fp32 engine: d / heads and mlp must be multiples of 4")
         self.kpad = _round_up(3 * spec.patch * spec.patch, 4)
         self.max_ws_bytes = int(max_ws_bytes)
-        self._keep = []
-        dev = self.device
-
-        def f32(t):
-            if t is None:
-                return None
-            x = t.detach().to(device=dev, dtype=torch.float32).contiguous()
-            self._keep.append(x)
-            return x
-
         pw = torch.zeros(spec.d, self.kpad, dtype=torch.float32)
         pw[:, : 3 * spec.patch * spec.patch] = weights["patch_w"].float()
         if weights["pos"].shape[0] != spec.tokens:
             raise ValueError(f"position embedding has {weights['pos'].shape[0]} rows, spec wants {spec.tokens}")
-        self._patch_w = f32(pw)
-        self._vecs = {k: f32(weights.get(k)) for k in ("patch_b", "pos", "pre_ln_g", "pre_ln_b")}
-        self._vecs["cls"] = f32(prefix_table(spec, weights))      # [d], or [1 + registers, d]: the class token, then the register tokens
-        n = len(weights["layers"])
-        self.n_layers = n
-        self._layers = (_lib.VitLayer * max(n, 1))()
-        for i, L in enumerate(weights["layers"]):
-            ent = self._layers[i]
-            for k in ("wqkv", "wo", "w1", "w2", "ln1_g", "ln1_b", "bqkv", "bo", "ls1", "ln2_g", "ln2_b", "b1", "b2", "ls2"):
-                v = f32(L.get(k))
-                setattr(ent, k, 0 if v is None else v.data_ptr())
-            if spec.qk_norm:                                                   # absent gains = ones
-                ent.qn_g, ent.kn_g = (f32(L[k] if L.get(k) is not None else torch.ones(spec.d)).data_ptr() for k in ("qn_g", "kn_g"))
-            ent.sqkv = 0
-            ent.s1 = 0
-        self._w = _lib.VitWeights()
-        self._w.patch_w = self._patch_w.data_ptr()
-        for k, v in self._vecs.items():
-            setattr(self._w, k, 0 if v is None else v.data_ptr())
-        self._w.layers = C.cast(self._layers, C.POINTER(_lib.VitLayer))
-        self._cfg = _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, spec.mlp, n, spec.tokens,
-                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), registers=spec.registers,
-                                   norm=_lib.NORM[spec.norm], qk_norm=int(spec.qk_norm))
-        self._ws: Dict[int, torch.Tensor] = {}
-        self._pinned = set()                 # batch sizes whose workspace a captured HIP graph refers to
-        import os
+        self.n_layers = n = len(weights["layers"])
+        held = _fill_vit_tables(self, pw, _vit_vector_table(spec, weights), _raw_vit_layers(spec, weights))
+        self._cfg = _plain_vit_config(spec, n, self.kpad)
         gemm = os.environ.get("VISREP_F32_GEMM", gemm)
         if gemm not in ("auto", "split", "native"):
             raise ValueError(f"gemm must be 'auto', 'split' or 'native', got {gemm!r}")
@@ -349,20 +369,14 @@ class VitEngineF32:
             with torch.cuda.device(self.device):
                 for i in range(n):
                     for k in ("wqkv", "wo", "w1", "w2"):
-                        wf = self._keep_by_ptr(getattr(self._layers[i], k))
-                        planes = torch.empty(wf.shape[0], npl * wf.shape[1], dtype=torch.bfloat16, device=dev)
+                        wf = held[i][k]
+                        planes = torch.empty(wf.shape[0], npl * wf.shape[1], dtype=torch.bfloat16, device=self.device)
                         _lib.check(self.lib.visrep_split_bf16_planes(_lib.ptr(wf), wf.stride(0), wf.shape[0], wf.shape[1], npl, _lib.ptr(planes),
                                                                      _lib.stream_ptr()), "visrep_split_bf16_planes")
                         self._keep.append(planes)
                         setattr(self._split_layers[i], k, planes.data_ptr())
             self._wsplit = _lib.VitWeights()
             self._wsplit.layers = C.cast(self._split_layers, C.POINTER(_lib.VitLayer))
-
-    def _keep_by_ptr(self, ptr: int) -> torch.Tensor:
-        for t in self._keep:
-            if t.data_ptr() == ptr:
-                return t
-        raise KeyError(ptr)
 
     def chunk(self) -> int:
         """Images per library call.  Bounded by the workspace budget, then picked for the GEMMs' tile rounds (best_chunk): the persistent
@@ -371,30 +385,17 @@ class VitEngineF32:
         3.98 (4 run)."""
         per = self.lib.visrep_vit_f32_workspace_bytes(C.byref(self._cfg), 1)
         cap = max(1, min(128, self.max_ws_bytes // max(per, 1)))
-        import os
         forced = int(os.environ.get("VISREP_F32_CHUNK", "0"))              # A/B knob (tools/)
         return min(forced, cap) if forced > 0 else best_chunk(self.spec.tokens, self.spec.d, cap)
 
-    def workspace(self, B: int) -> torch.Tensor:
-        ws = self._ws.get(B)
-        if ws is None:
-            for old in [b for b in self._ws if b not in self._pinned][: max(0, len(self._ws) - len(self._pinned) - 5)]:
-                self._ws.pop(old)
-            ws = torch.empty(self.lib.visrep_vit_f32_workspace_bytes(C.byref(self._cfg), B), dtype=torch.uint8, device=self.device)
-            self._ws[B] = ws
-        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            self._pinned.add(B)                 # a captured graph refers to this pointer: never evicted
-        return ws
+    def _workspace_bytes(self, B: int) -> int:
+        return self.lib.visrep_vit_f32_workspace_bytes(C.byref(self._cfg), B)
 
     @torch.no_grad()
     def forward(self, pixels: torch.Tensor, n_layers: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         s = self.spec
-        if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != s.image_size or pixels.shape[3] != s.image_size:
-            raise ValueError(f"Input image size {tuple(pixels.shape)} doesn't match tower ({s.image_size}*{s.image_size}).")
-        n_layers = self.n_layers if n_layers is None else n_layers
-        if not 0 <= n_layers <= self.n_layers:
-            raise ValueError("n_layers out of range")
-        px = pixels.to(device=self.device, dtype=torch.float32).contiguous()
+        px = self._pixels(pixels)
+        n_layers = self._state(n_layers, "n_layers out of range")
         B = px.shape[0]
         if out is None:
             out = torch.empty(B, s.tokens, s.d, dtype=torch.float32, device=self.device)
@@ -445,61 +446,29 @@ def best_chunk(tokens: int, d: int, cap: int, cus: Optional[int] = None) -> int:
     return max(c for c, e in effs.items() if e >= top - 0.01)
 
 
-class VitEngineCPU:
+class VitEngineCPU(_TowerEngine):
     """The same tower on HOST cores (visrep_vit_forward_cpu, csrc/host_twins.hip): plain C++ fp32 on host threads.  BASELINE configs[0]
     ("vision_tower feature-extract on 32 COCO images, CPU float32 - plumbing, no GPU") and SURVEY §8b's `*_cpu` twins.  Built ONLY when the
     caller asks for device "cpu" explicitly (make_engine(..., device="cpu"); a tower config with device="cpu") - the GPU engines never fall
     back to it.  forward() takes and returns CPU fp32 tensors."""
 
-    def __init__(self, spec: ViTSpec, weights: dict, threads: Optional[int] = None):
-        self.lib = _lib.load()
-        self.spec = spec
-        self.device = torch.device("cpu")
-        self.threads = int(threads) if threads else 0
-        self._keep = []
+    PIXEL_DTYPES = (torch.float32,)
 
-        def f32(t):
-            if t is None:
-                return None
-            x = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-            self._keep.append(x)
-            return x
+    def __init__(self, spec: ViTSpec, weights: dict, threads: Optional[int] = None):
+        super().__init__(_lib.load(), spec, "cpu")
+        self.threads = int(threads) if threads else 0
         if weights["pos"].shape[0] != spec.tokens:
             raise ValueError(f"position embedding has {weights['pos'].shape[0]} rows, spec wants {spec.tokens}")
         self.kpad = 3 * spec.patch * spec.patch
-        self._patch_w = f32(weights["patch_w"].reshape(spec.d, -1)[:, : self.kpad])
-        self._vecs = {k: f32(weights.get(k)) for k in ("patch_b", "pos", "pre_ln_g", "pre_ln_b")}
-        self._vecs["cls"] = f32(prefix_table(spec, weights))      # [d], or [1 + registers, d]: the class token, then the register tokens
-        n = len(weights["layers"])
-        self.n_layers = n
-        self._layers = (_lib.VitLayer * max(n, 1))()
-        for i, L in enumerate(weights["layers"]):
-            ent = self._layers[i]
-            for k in ("wqkv", "wo", "w1", "w2", "ln1_g", "ln1_b", "bqkv", "bo", "ls1", "ln2_g", "ln2_b", "b1", "b2", "ls2"):
-                v = f32(L.get(k))
-                setattr(ent, k, 0 if v is None else v.data_ptr())
-            if spec.qk_norm:                                                   # absent gains = ones
-                ent.qn_g, ent.kn_g = (f32(L[k] if L.get(k) is not None else torch.ones(spec.d)).data_ptr() for k in ("qn_g", "kn_g"))
-            ent.sqkv = 0
-            ent.s1 = 0
-        self._w = _lib.VitWeights()
-        self._w.patch_w = self._patch_w.data_ptr()
-        for k, v in self._vecs.items():
-            setattr(self._w, k, 0 if v is None else v.data_ptr())
-        self._w.layers = C.cast(self._layers, C.POINTER(_lib.VitLayer))
-        self._cfg = _lib.VitConfig(spec.image_size, spec.patch, spec.d, spec.heads, spec.mlp, n, spec.tokens,
-                                   int(spec.has_cls), int(spec.pre_ln), _lib.ACT[spec.act], self.kpad, float(spec.eps), registers=spec.registers,
-                                   norm=_lib.NORM[spec.norm], qk_norm=int(spec.qk_norm))
+        self.n_layers = n = len(weights["layers"])
+        _fill_vit_tables(self, weights["patch_w"].reshape(spec.d, -1)[:, : self.kpad], _vit_vector_table(spec, weights), _raw_vit_layers(spec, weights))
+        self._cfg = _plain_vit_config(spec, n, self.kpad)
 
     @torch.no_grad()
     def forward(self, pixels: torch.Tensor, n_layers: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         s = self.spec
-        if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != s.image_size or pixels.shape[3] != s.image_size:
-            raise ValueError(f"Input image size {tuple(pixels.shape)} doesn't match tower ({s.image_size}*{s.image_size}).")
-        n_layers = self.n_layers if n_layers is None else n_layers
-        if not 0 <= n_layers <= self.n_layers:
-            raise ValueError("n_layers out of range")
-        px = pixels.detach().to(device="cpu", dtype=torch.float32).contiguous()
+        px = self._pixels(pixels)
+        n_layers = self._state(n_layers, "n_layers out of range")
         B = px.shape[0]
         if out is None:
             out = torch.empty(B, s.tokens, s.d, dtype=torch.float32)
@@ -719,7 +688,7 @@ def mhsa_prefix(qk: torch.Tensor, vt: torch.Tensor, vpre: torch.Tensor, B: int, 
 
 
 # ------------------------------------------------------------------------------------------------ ConvNeXt
-class ConvNextEngine:
+class ConvNextEngine(_TowerEngine):
     """One ConvNeXt tower on one GPU (visrep_convnext_forward): forward(pixels, n_stages) returns hidden_states[n_stages] of HF ConvNextModel as
     bf16 token rows [B, H_s W_s, C_s] - index 0 = the stem output, 1 .. 4 = the stage outputs.  bf16 on the GPU only: there is no fp32 and no
     host ConvNeXt engine, and asking for one is an error, never a fallback."""
@@ -728,19 +697,12 @@ class ConvNextEngine:
         from . import convnext_weights as CW
         if device is not None and torch.device(device).type == "cpu":
             raise ValueError("ConvNeXt towers have no host engine (device='cpu'): only the bf16 HIP engine exists")
-        self.lib = _lib.require_gpu()
-        self.spec = spec
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        super().__init__(_lib.require_gpu(), spec, device)
         self.n_layers = 4                                  # the tower protocol's name for "last hidden-state index"
         ensure_scratch(self.device)
-        self._keep = []
 
         def dev(t):
-            if t is None:
-                return 0
-            x = t.detach().to(device=self.device).contiguous()
-            self._keep.append(x)
-            return x.data_ptr()
+            return _addr(self._hold(t))
 
         D = CW.device_layout(spec, weights)
         nblk = sum(spec.depths)
@@ -760,32 +722,18 @@ class ConvNextEngine:
                 i += 1
         self._w.blocks = C.cast(self._blocks, C.POINTER(_lib.ConvNextBlock))
         self._cfg = _lib.ConvNextConfig(spec.image_size, 64, (C.c_int * 4)(*spec.depths), (C.c_int * 4)(*spec.hidden_sizes), float(spec.eps))
-        self._ws: Dict[int, torch.Tensor] = {}
 
-    def workspace(self, B: int) -> torch.Tensor:
-        ws = self._ws.get(B)
-        if ws is None:
-            nbytes = self.lib.visrep_convnext_workspace_bytes(C.byref(self._cfg), B)
-            if nbytes == 0:
-                raise RuntimeError(f"visrep_convnext_workspace_bytes refused the tower: {_lib.last_error()}")
-            if len(self._ws) > 4:
-                self._ws.clear()
-            ws = self._ws[B] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        return ws
+    def _workspace_bytes(self, B: int) -> int:
+        nbytes = self.lib.visrep_convnext_workspace_bytes(C.byref(self._cfg), B)
+        if nbytes == 0:
+            raise RuntimeError(f"visrep_convnext_workspace_bytes refused the tower: {_lib.last_error()}")
+        return nbytes
 
     @torch.no_grad()
     def forward(self, pixels: torch.Tensor, n_stages: Optional[int] = None, out: Optional[torch.Tensor] = None, n_layers: Optional[int] = None) -> torch.Tensor:
         s = self.spec
-        if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != s.image_size or pixels.shape[3] != s.image_size:
-            raise ValueError(f"Input image size {tuple(pixels.shape)} doesn't match tower ({s.image_size}*{s.image_size}).")
-        if n_stages is None:
-            n_stages = 4 if n_layers is None else n_layers
-        if not 0 <= n_stages <= 4:
-            raise ValueError("n_stages out of range (0 = stem output, 1 .. 4 = stage outputs)")
-        px = pixels.to(self.device)
-        if px.dtype not in (torch.float32, torch.bfloat16):
-            px = px.float()
-        px = px.contiguous()
+        px = self._pixels(pixels)
+        n_stages = self._state(n_layers if n_stages is None else n_stages, "n_stages out of range (0 = stem output, 1 .. 4 = stage outputs)")
         B = px.shape[0]
         if out is None:
             out = torch.empty(B, s.grid(n_stages) ** 2, s.width(n_stages), dtype=torch.bfloat16, device=self.device)
@@ -856,27 +804,24 @@ def ln_space_to_depth2_cpu(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, C:
 
 
 # ------------------------------------------------------------------------------------------------ SAM ViT
-class SamEngine:
+class SamEngine(_TowerEngine):
     """One SAM ViT tower on one GPU (visrep_sam_forward): forward(pixels, n_state) returns state n_state of HF SamVisionModel as bf16 token
     rows - 0 = patch embedding + positions, 1 .. L = the block outputs [B, g g, d], L + 1 = the neck output [B, g g, out_channels] - and stops
     after it.  bf16 on the GPU only: there is no fp32 and no host SAM engine, and asking for one is an error, never a fallback."""
+
+    WS_KEEP = 0                                            # the workspaces are the large ones: one unpinned batch size at a time
 
     def __init__(self, spec, weights: dict, device: Optional[torch.device] = None):
         from . import sam_weights as SW
         if device is not None and torch.device(device).type == "cpu":
             raise ValueError("SAM towers have no host engine (device='cpu'): only the bf16 HIP engine exists")
-        self.lib = _lib.require_gpu()
-        self.spec = spec
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        super().__init__(_lib.require_gpu(), spec, device)
         self.n_layers = spec.layers + 1                    # the tower protocol's name for "last hidden-state index"
         self.kpad = _round_up(3 * spec.patch * spec.patch, 64)
         ensure_scratch(self.device)
-        self._keep = []
 
         def dev(t):
-            x = t.detach().to(device=self.device).contiguous()
-            self._keep.append(x)
-            return x.data_ptr()
+            return _addr(self._hold(t))
 
         if len(weights["layers"]) != spec.layers:
             raise ValueError(f"weights have {len(weights['layers'])} layers, spec wants {spec.layers}")
@@ -894,31 +839,19 @@ class SamEngine:
             mask |= 1 << i
         self._cfg = _lib.SamConfig(spec.image_size, spec.patch, spec.d, spec.layers, spec.heads, spec.mlp, spec.window, spec.out_channels, self.kpad,
                                    mask, float(spec.eps), 1e-6)
-        self._ws: Dict[int, torch.Tensor] = {}
 
-    def workspace(self, B: int) -> torch.Tensor:
-        ws = self._ws.get(B)
-        if ws is None:
-            nbytes = self.lib.visrep_sam_workspace_bytes(C.byref(self._cfg), B)
-            if nbytes == 0:
-                raise RuntimeError(f"visrep_sam_workspace_bytes refused the tower: {_lib.last_error()}")
-            self._ws.clear()
-            ws = self._ws[B] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        return ws
+    def _workspace_bytes(self, B: int) -> int:
+        nbytes = self.lib.visrep_sam_workspace_bytes(C.byref(self._cfg), B)
+        if nbytes == 0:
+            raise RuntimeError(f"visrep_sam_workspace_bytes refused the tower: {_lib.last_error()}")
+        return nbytes
 
     @torch.no_grad()
     def forward(self, pixels: torch.Tensor, n_state: Optional[int] = None, out: Optional[torch.Tensor] = None, n_layers: Optional[int] = None) -> torch.Tensor:
         s = self.spec
-        if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != s.image_size or pixels.shape[3] != s.image_size:
-            raise ValueError(f"Input image size {tuple(pixels.shape)} doesn't match tower ({s.image_size}*{s.image_size}).")
-        if n_state is None:
-            n_state = s.layers + 1 if n_layers is None else n_layers
-        if not 0 <= n_state <= s.layers + 1:
-            raise ValueError(f"n_state out of range (0 = embeddings, 1 .. {s.layers} = blocks, {s.layers + 1} = the neck)")
-        px = pixels.to(self.device)
-        if px.dtype not in (torch.float32, torch.bfloat16):
-            px = px.float()
-        px = px.contiguous()
+        px = self._pixels(pixels)
+        n_state = self._state(n_layers if n_state is None else n_state,
+                              f"n_state out of range (0 = embeddings, 1 .. {s.layers} = blocks, {s.layers + 1} = the neck)")
         B = px.shape[0]
         if out is None:
             out = torch.empty(B, s.grid ** 2, s.width(n_state), dtype=torch.bfloat16, device=self.device)

@@ -8,6 +8,7 @@ is used only to READ checkpoints/configs when they exist locally.
 """
 from __future__ import annotations
 
+import json
 import os
 from types import SimpleNamespace
 from typing import Optional
@@ -71,7 +72,6 @@ def _find_local_checkpoint(name: str) -> Optional[str]:
 
 def _processor_crop(path: str) -> Optional[int]:
     """crop_size of the checkpoint's preprocessor_config.json (the input size the reference's AutoImageProcessor produces)."""
-    import json
     f = os.path.join(path, "preprocessor_config.json")
     if not os.path.exists(f):
         return None
@@ -83,6 +83,25 @@ def _processor_crop(path: str) -> Optional[int]:
     if isinstance(c, dict):
         c = c.get("height") or c.get("shortest_edge")
     return int(c) if c else None
+
+
+def _processor_stats(path: Optional[str], mean, std):
+    """image_mean / image_std of the checkpoint's preprocessor_config.json when the directory has one, else the given defaults."""
+    f = os.path.join(path, "preprocessor_config.json") if path else None
+    if f and os.path.exists(f):
+        with open(f) as fh:
+            pc = json.load(fh)
+        mean, std = tuple(pc.get("image_mean", mean)), tuple(pc.get("image_std", std))
+    return mean, std
+
+
+def _no_checkpoint(name: str) -> OSError:
+    return OSError(f"{name} is not a local checkpoint directory and is not in the offline HF cache "
+                   "(set VISREP_SYNTHETIC_WEIGHTS=1 or args.synthetic_weights for deterministic random-init weights)")
+
+
+def _no_architecture(name: str) -> OSError:              # like from_pretrained on a name that is neither a directory nor cached
+    return OSError(f"{name} is not a local checkpoint directory, is not in the offline HF cache and has no built-in architecture")
 
 
 def _load_state_dict(path: str):
@@ -146,8 +165,12 @@ class HipViTTower(nn.Module):
             base = spec.at_resolution(native)
             w = VW.synthetic_weights(base, seed=1)
             return VW.weights_at_resolution(base, w, spec.image_size)
-        raise OSError(f"{self.vision_tower_name} is not a local checkpoint directory and is not in the offline HF cache "
-                      "(set VISREP_SYNTHETIC_WEIGHTS=1 or args.synthetic_weights for deterministic random-init weights)")
+        raise _no_checkpoint(self.vision_tower_name)
+
+    def _config_for(self, spec):
+        """What the tower protocol reads of the HF config, from a spec."""
+        return SimpleNamespace(hidden_size=spec.d, image_size=spec.image_size, patch_size=spec.patch, num_hidden_layers=spec.layers,
+                               num_attention_heads=spec.heads, intermediate_size=spec.mlp)
 
     def _config_only(self):
         path = _find_local_checkpoint(self.vision_tower_name)
@@ -156,16 +179,11 @@ class HipViTTower(nn.Module):
             cfg = AutoConfig.from_pretrained(path)
             if getattr(cfg, "model_type", "") in ("internvl", "internvl_vision"):
                 # an InternVL checkpoint: the tower is its vision_config, whose image_size / patch_size are pairs - the protocol wants integers
-                spec = VW.spec_from_hf_config(cfg, self.vision_tower_name)
-                return SimpleNamespace(hidden_size=spec.d, image_size=spec.image_size, patch_size=spec.patch, num_hidden_layers=spec.layers,
-                                       num_attention_heads=spec.heads, intermediate_size=spec.mlp)
+                return self._config_for(VW.spec_from_hf_config(cfg, self.vision_tower_name))
             return cfg
-        if self.vision_tower_name not in VW.SPECS:           # like from_pretrained on a name that is neither a directory nor cached
-            raise OSError(f"{self.vision_tower_name} is not a local checkpoint directory, is not in the offline HF cache and has no built-in "
-                          "architecture")
-        spec = VW.SPECS[self.vision_tower_name]
-        return SimpleNamespace(hidden_size=spec.d, image_size=spec.image_size, patch_size=spec.patch,
-                               num_hidden_layers=spec.layers, num_attention_heads=spec.heads, intermediate_size=spec.mlp)
+        if self.vision_tower_name not in VW.SPECS:
+            raise _no_architecture(self.vision_tower_name)
+        return self._config_for(VW.SPECS[self.vision_tower_name])
 
     def _make_image_processor(self, spec):
         from .image_processing import default_image_processor
@@ -178,13 +196,11 @@ class HipViTTower(nn.Module):
             spec, w = VW.weights_at_resolution(spec, w, self._img_size)
         self.spec = spec
         self.image_processor = self._make_image_processor(spec)
-        cfg = SimpleNamespace(hidden_size=spec.d, image_size=spec.image_size, patch_size=spec.patch,
-                              num_hidden_layers=spec.layers, num_attention_heads=spec.heads, intermediate_size=spec.mlp)
         fp32 = self._precision in ("fp32", "float32")
         eng = engine.make_engine(spec, w, self._device, "fp32" if fp32 else "bf16", products=self._products if fp32 else None)
         if isinstance(eng, engine.VitEngineCPU):                            # args.device = "cpu": the host twin (explicit opt-in; BASELINE configs[0])
             fp32 = True
-        self.vision_tower = _EngineModule(eng, cfg, torch.float32 if fp32 else torch.bfloat16)
+        self.vision_tower = _EngineModule(eng, self._config_for(spec), torch.float32 if fp32 else torch.bfloat16)
         self.vision_tower.requires_grad_(False)
         self.is_loaded = True
 
@@ -237,3 +253,62 @@ class HipViTTower(nn.Module):
     @property
     def num_patches(self):
         return (self.config.image_size // self.config.patch_size) ** 2
+
+
+class PatchMapTower(HipViTTower):
+    """Towers without a class token, bf16 on the GPU only (ConvNeXt, SAM): every row of the selected state is a feature, so `select_feature` is
+    'patch' only.  A subclass names its weights module (WEIGHTS: SPECS, pack_hf_state_dict, synthetic_weights), its engine factory in
+    engine.py (ENGINE) and the default image statistics (MEAN, STD), and supplies _hf_spec(cfg, path) and _config_for(spec); _spec and
+    _retarget are there to be extended."""
+    DEFAULT_SELECT_FEATURE = "patch"
+    WEIGHTS = ENGINE = MEAN = STD = None
+
+    def __init__(self, vision_tower, args, delay_load=False):
+        self._require_patch(getattr(args, "mm_vision_select_feature", self.DEFAULT_SELECT_FEATURE))      # before anything is loaded
+        super().__init__(vision_tower, args, delay_load=delay_load)
+
+    @staticmethod
+    def _require_patch(feature):
+        if feature != "patch":                               # the protocol's error: there is no class token to keep
+            raise ValueError(f"Unexpected select feature: {feature}")
+
+    # ------------------------------------------------------------------ loading
+    def _spec(self, path):
+        if path is not None:
+            from transformers import AutoConfig
+            return self._hf_spec(AutoConfig.from_pretrained(path), path)
+        if self.vision_tower_name in self.WEIGHTS.SPECS:
+            return self.WEIGHTS.SPECS[self.vision_tower_name]
+        raise _no_architecture(self.vision_tower_name)
+
+    def _retarget(self, spec):
+        return spec
+
+    def _config_only(self):
+        return self._config_for(self._retarget(self._spec(_find_local_checkpoint(self.vision_tower_name))))
+
+    def _make_image_processor(self, spec, path=None):
+        """Resize + centre crop to the spec side; mean / std from the directory's preprocessor_config.json when it has one, else the family's."""
+        from .image_processing import SimpleImageProcessor
+        return SimpleImageProcessor(spec.image_size, spec.image_size, *_processor_stats(path, self.MEAN, self.STD))
+
+    def load_model(self):
+        from .... import engine
+        path = _find_local_checkpoint(self.vision_tower_name)
+        spec = self._spec(path)
+        if path is not None:
+            w = self.WEIGHTS.pack_hf_state_dict(_load_state_dict(path), spec)
+        elif self._synthetic:
+            w = self.WEIGHTS.synthetic_weights(spec, seed=1)
+        else:
+            raise _no_checkpoint(self.vision_tower_name)
+        self.spec = spec = self._retarget(spec)              # after the packer: it reads the checkpoint's own shape
+        self.image_processor = self._make_image_processor(spec, path)
+        eng = getattr(engine, self.ENGINE)(spec, w, self._device, "fp32" if self._precision in ("fp32", "float32") else self._precision)
+        self.vision_tower = _EngineModule(eng, self._config_for(spec), torch.bfloat16)
+        self.vision_tower.requires_grad_(False)
+        self.is_loaded = True
+
+    def feature_select(self, image_forward_outs):
+        self._require_patch(self.select_feature)
+        return image_forward_outs.hidden_states[self.select_layer]       # every row is a patch: nothing to drop
