@@ -744,7 +744,9 @@ int visrep_conv3x3_bf16_halo(const void* x, int B, int H, int W, int C, const vo
  * per lane and k-step, zeros outside the image), nothing is staged; the epilogue is the GEMM kernels' (bias, 16-byte stores) and optionally leaves
  * the GroupNorm partial sums of the output (gn_partial as visrep_conv3x3_bf16_gn: visrep_conv_gn_partial_bytes(B, H W, groups) bytes; NULL = none).
  * Supported: Cout = 128, W % 16 == 0, H W % 64 == 0 (% 128 with partial sums).  Equals visrep_im2col3x3 + visrep_gemm_bf16 up to the order of
- * the fp32 sum inside an MFMA. */
+ * the fp32 sum inside an MFMA.  K is padded from 72 to 96: weight columns 72 .. 95 ARE read (against zero pixel operands) and must be zero - a
+ * finite value there is not promised to leave the result unchanged, a NaN or Inf poisons it; columns >= 96 are never read.  ldw and ldc must be
+ * multiples of 8 (refused otherwise); out may be 8-byte aligned only (narrow stores). */
 int visrep_conv3x3_c8_supported(int B, int H, int W, int Cout);
 int visrep_conv3x3_c8_bf16(const void* x, int B, int H, int W, const void* Wt, int ldw, const float* bias, void* out, int ldc, int Cout,
                            void* gn_partial, int groups, void* stream);

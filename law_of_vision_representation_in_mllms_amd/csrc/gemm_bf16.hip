@@ -516,6 +516,8 @@ bool conv5_ok(const GemmArgs& a, int variant) {
 }
 }  // namespace
 
+// The routing rules below (and try_split_k / dispatch_one above) are restated in Python for the CPU-side plan assertions of the contract tests:
+// tests/_gemm_cases.py (expected_family) and tests/_conv_cases.py (route_plan, split_k_slices).  Change them together.
 int visrep_gemm_dispatch(const GemmArgs& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0) return visrep_set_error(VISREP_ERR_SHAPE, "gemm: empty problem");
     if (a.N % 64 != 0 || a.K % BK != 0) return visrep_set_error(VISREP_ERR_SHAPE, "gemm: N and K must be multiples of 64");

@@ -145,15 +145,21 @@ def gemm_reference(kind, a, w, bias, *, act=None, resid=None, ls=None, ln=None):
     """float64 result and per-element bound of one GEMM epilogue.  a [M, K], w [N, K]: fp32 tensors holding bf16 values; bias [N] fp32 or None;
     act: a name of ACTS (kind 'act'); resid [M, N] fp32 holding bf16 values and ls [N] fp32 or None (kind 'resid'); ln = (rt [M, 2] fp32, s [N] fp32)
     or None.  kind 'vt' returns the LOGICAL [M, N] result (compare through vt_unpermute).  Derivation: module docstring."""
-    assert kind in KINDS
     A, W = a.double(), w.double()
-    K = A.shape[1]
-    acc = A @ W.t()
-    mag = A.abs() @ W.abs().t()
-    b = torch.zeros(W.shape[0], dtype=torch.float64) if bias is None else bias.double()
+    return epilogue_reference(kind, A @ W.t(), A.abs() @ W.abs().t(), A.shape[1], bias, act=act, resid=resid, ls=ls, ln=ln)
+
+
+def epilogue_reference(kind, acc, mag, K, bias, *, act=None, resid=None, ls=None, ln=None, dacc=None):
+    """The epilogue half of `gemm_reference` for an accumulation computed elsewhere (tests/_conv_cases.py: a convolution is the same sum of K
+    products): acc [M, N] = the float64 sum, mag [M, N] = the same sum of magnitudes, K = the number of products the device adds per element.
+    dacc (optional, [M, N]): an absolute error of acc that is known on top of its summation error (operands that may round the other way)."""
+    assert kind in KINDS
+    b = torch.zeros(acc.shape[1], dtype=torch.float64, device=acc.device) if bias is None else bias.double()
     if ln is None:
         z = acc + b
         dz = (K + 8) * U * (mag + b.abs())
+        if dacc is not None:
+            dz = dz + dacc
     else:
         rt, s = ln[0].double(), ln[1].double()
         rstd, t = rt[:, :1], rt[:, 1:2]
